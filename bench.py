@@ -2,9 +2,17 @@
 """bench.py -- the headline measurement (BASELINE.json): env steps/s and TRPO iteration
 time of the batched rollout + TRPO update at 4096 Swimmer-style envs per MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: either pre-launched as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`,
-   or plainly -- bench.py then re-executes itself under torch.distributed.run with N ranks on 127.0.0.1)
+   or plainly -- bench.py then starts itself as a child process under torch.distributed.run with N ranks on
+   127.0.0.1 and exits with its return code)
+
+A plain run sets up, warms up, times the K iterations and prints the JSON line (the headline fields, the phase
+times and the rollout roofline, all from the timed iterations themselves).  Everything that takes runs of its own
+-- roofline_mfma, roofline_step_kernel, roofline_scan, cpu_baseline, and for N > 1 collective_ms_per_iter and
+other_sum_path -- is measured only with --full.  --dump-outputs DIR writes what the last timed iteration computed
+(the updated policy parameters and a fixed, seeded sample of 256 env columns of the processed batch) as
+DIR/<name>.npy, so that two builds can be compared output for output.
 
 One "step" = one full TRPO iteration of BatchPolopt.train (sampler.obtain_samples ->
 process_samples -> log_diagnostics -> optimize_policy) on a batch of
@@ -176,6 +184,29 @@ def scan_rooflines(torch, algo, traj, reps=20):
     return out
 
 
+def last_outputs(policy, samples, n_cols=256):
+    """What a caller of the timed iteration receives from it, as host arrays: the policy parameters after the update
+    and the processed batch (observations, actions, means, rewards, advantages, returns, baseline values, validity)
+    on a fixed, seeded sample of ``n_cols`` env columns, every time step of each.  Entries outside the valid samples
+    carry no meaning and are written as 0."""
+    import numpy as np
+    import torch
+    traj = samples["_traj"]
+    cols = np.sort(np.random.RandomState(0).choice(traj.N, min(traj.N, n_cols), replace=False))
+    idx = torch.as_tensor(cols, device=traj.device)
+    valid = traj.valid.index_select(-1, idx).cpu().numpy().astype(bool)
+    out = {"policy_params": policy.get_param_values().astype(np.float64),
+           "env_columns": cols.astype(np.float64), "valid": valid.astype(np.float32),
+           "dones": traj.dones.index_select(-1, idx).cpu().numpy().astype(np.float32)}
+    for name in ("obs", "actions", "means", "rewards", "advantages", "returns", "baselines"):
+        x = getattr(traj, name)
+        if x is None:
+            continue
+        x = x.index_select(-1, idx).cpu().numpy()
+        out[name] = np.where(valid, x, 0).astype(np.float64 if x.dtype == np.float64 else np.float32)
+    return out
+
+
 def self_launch_argv(n_gpus, argv, port=None):
     """The command a plain `python bench.py --gpus N` turns itself into: one rank per GPU of this node
     under torch.distributed.run, rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
@@ -209,7 +240,11 @@ def main():
     ap.add_argument("--n-envs", type=int, default=None, help="envs per GPU (default: the workload's 4096)")
     ap.add_argument("--hidden", default=None, help="policy hidden sizes, e.g. 100,50,25 (side lines; default: the "
                                                    "workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: "
+                                                        "rooflines, CPU baseline, collective timing, other sum path")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed iteration's outputs "
+                                                                        "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-port sampling")
     args = ap.parse_args()
 
@@ -220,15 +255,26 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    assert torch.cuda.is_available(), "bench.py needs a HIP device"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # The ranks run in a child process tree and this process only waits for them: it never touches the GPU itself
+        # (the device count comes from a short-lived child), so a world of N ranks keeps N processes on the devices.
+        # The ranks share this process's stdout (rank 0 prints the one JSON line); a SIGTERM is passed on to them.
+        import signal
+        import subprocess
         # (RLLAB_DIST_BACKEND=gloo is the test mode in which ranks may share a device)
-        if args.gpus > torch.cuda.device_count() and os.environ.get("RLLAB_DIST_BACKEND", "nccl") == "nccl":
-            sys.exit("bench.py --gpus %d: this node has %d GPUs" % (args.gpus, torch.cuda.device_count()))
+        if os.environ.get("RLLAB_DIST_BACKEND", "nccl") == "nccl":
+            n_dev = int(subprocess.check_output([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"],
+                                                universal_newlines=True).split()[-1])
+            if args.gpus > n_dev:
+                sys.exit("bench.py --gpus %d: this node has %d GPUs" % (args.gpus, n_dev))
         cmd = self_launch_argv(args.gpus, sys.argv[1:])
         sys.stderr.write("[bench] launching %d ranks: %s\n" % (args.gpus, " ".join(cmd)))
         sys.stderr.flush()
-        os.execv(cmd[0], cmd)
+        child = subprocess.Popen(cmd)
+        signal.signal(signal.SIGTERM, lambda signum, frame: child.terminate())
+        rc = child.wait()
+        sys.exit(rc if rc >= 0 else 128 - rc)
+    assert torch.cuda.is_available(), "bench.py needs a HIP device"
     if args.gpus != world:
         sys.exit("bench.py --gpus %d under WORLD_SIZE=%d" % (args.gpus, world))
     device_index = local_rank % torch.cuda.device_count()
@@ -345,9 +391,10 @@ def main():
 
     itr_base = [0]
 
-    def timed_run(warmup, steps):
+    def timed_run(warmup, steps, capture=None):
         """``warmup`` untimed + ``steps`` timed iterations, bracketed by barrier + synchronize on both sides; returns the
-        run's record (max-over-ranks wall time, phase times of THIS rank and of every rank, collectives)."""
+        run's record (max-over-ranks wall time, phase times of THIS rank and of every rank, collectives).  ``capture``
+        is called right after the timed region, before anything else runs an iteration."""
         del timed_events[:], host_stamps[:]
         pending.clear()
         base = itr_base[0]
@@ -371,13 +418,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed_ = time.perf_counter() - t0
+        if capture is not None:
+            capture()
         acct = D.accounting()
         rec = dict(collectives_per_iter=acct["count"] / float(steps),
                    peer_reductions_per_iter=acct.get("peer", 0) / float(steps),   # in-stream rl_peer_allreduce_sum launches
                    collective_bytes_per_iter=acct["bytes"] / float(steps), collective_ms_per_iter=None,
                    update_sum_path=D.peer_status()[0] if dist.is_initialized() else None)
         extra = 0
-        if D.is_distributed():
+        if D.is_distributed() and args.full:
             # a few extra iterations with every collective bracketed by a device synchronise (host clock):
             # what the exchange family costs per iteration, outside the timed region
             D.reset_accounting(timing=True)
@@ -409,14 +458,21 @@ def main():
         rec["rank_skew_ms"] = {c: round(float(rows[:, j].max() - rows[:, j].min()), 4) for j, c in enumerate(cols)}
         return rec
 
-    run = timed_run(args.warmup, args.steps)
-    # N > 1: the SAME invocation then times the other reduction path of the update's sums (gradient, Fisher-vector
+    outputs = {}
+    run = timed_run(args.warmup, args.steps,
+                    capture=(lambda: outputs.update(last_outputs(policy, last["samples"])))
+                    if args.dump_outputs and rank == 0 else None)
+    if outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+    # --full, N > 1: the SAME invocation then times the other reduction path of the update's sums (gradient, Fisher-vector
     # products) -- the in-stream peer all-reduce over hipIpc mailboxes (csrc/peer_kernels.hip) against the backend's
     # all-reduce (RCCL) -- so that one lease of an 8-GPU node answers which is faster.  The headline fields are the
     # backend's unless RLLAB_PEER_ALLREDUCE=1 asked for the peer path from the start; the other path's record rides
     # along as `other_sum_path`.  (Skipped when the pre-flight refused the peer path, or with RLLAB_BENCH_ONE_PATH=1.)
     other = None
-    if world > 1 and not os.environ.get("RLLAB_BENCH_ONE_PATH") and run["update_sum_path"] == "backend" \
+    if args.full and world > 1 and not os.environ.get("RLLAB_BENCH_ONE_PATH") and run["update_sum_path"] == "backend" \
             and not os.environ.get("RLLAB_PEER_ALLREDUCE"):
         os.environ["RLLAB_PEER_ALLREDUCE"] = "1"
         try:
@@ -490,7 +546,7 @@ def main():
     mfma_real_per_tile = macs_real * 32 / 2048.0
     fvp_ms = None
     fvp_variant = 0
-    ops = policy.fused_ops() if wl["algo"] == "trpo" else None
+    ops = policy.fused_ops() if wl["algo"] == "trpo" and args.full else None
     if ops is not None:
         from rllab_amd.algos.npo import npo_inputs
         inp = npo_inputs(policy, last["samples"])
@@ -666,14 +722,14 @@ def main():
                 acc[5] += host_stamps[i + 1][0] - h[5]
         for nm, v in zip(names, acc):
             sys.stderr.write("host %-36s %8.1f us / iteration\n" % (nm, v / n * 1e6))
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # The per-step VecEnv boundary kernel (rl_vecenv_step) at a chip-filling size: the one kernel of the path
         # the HBM roofline really applies to (the fused rollout keeps state in registers).  Timed live with HIP
         # events, same recipe as tools/step_kernel_roofline.py; algorithmic bytes per env-step =
         # 4 (2 S + Da + Do + 1) + 1 + 8 (ts read + write).
         out["roofline_step_kernel"] = [step_kernel_roofline(torch, k) for k in sorted({0, env_kind})]
         out["roofline_scan"] = scan_rooflines(torch, algo, last["samples"]["_traj"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # (1) the reference's own sampler, unmodified, in a child process (rllab must resolve to the reference there)
         from oracle import cpu_sampler, ref_sampler
         theta_host = policy.get_param_values()

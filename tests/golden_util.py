@@ -24,3 +24,23 @@ def unpack_paths(g):
 
 STAT_KEYS = ['AverageDiscountedReturn', 'AverageReturn', 'ExplainedVariance', 'NumTrajs', 'Entropy',
              'Perplexity', 'StdReturn', 'MaxReturn', 'MinReturn']
+
+
+REF_RUNS = "ref_runs"      # oracle/make_golden_refruns.py: the reference's own executor / sampler loop, recorded
+
+
+def ref_run(case, live=None):
+    """The reference's output for one recorded case of tests/golden/ref_runs.npz (arrays by name, ``modules`` as the
+    dict the child reported).  ``live``, where the reference is staged: run it now as well and require the recording."""
+    import json
+    g = load(REF_RUNS)
+    prefix = case + "/"
+    rec = {k[len(prefix):]: g[k] for k in g.files if k.startswith(prefix)}
+    assert rec, "no recorded reference run %r: regenerate with `python oracle/make_golden_refruns.py`" % case
+    rec["modules"] = json.loads(str(rec["modules"]))
+    if live is not None:
+        out = live()
+        assert set(out) == set(rec), (case, sorted(set(out) ^ set(rec)))
+        for k, v in rec.items():
+            assert (out[k] == v) if k == "modules" else np.array_equal(np.asarray(out[k]), v), (case, k)
+    return rec

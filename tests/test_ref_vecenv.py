@@ -13,8 +13,11 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAGED = os.path.join(ROOT, "oracle", "_ref", "sandbox", "rocky", "tf", "envs", "vec_env_executor.py")
-needs_ref = pytest.mark.skipif(not (os.path.isfile(STAGED) or os.path.isdir("/root/reference")),
-                               reason="no staged reference (run oracle/make_ref.py in the build container)")
+HAVE_REF = os.path.isfile(STAGED)       # build() stages it wherever the reference tree is present
+needs_ref = pytest.mark.skipif(not HAVE_REF, reason="no staged reference (oracle/make_ref.py, run by build())")
+# the lock-step cases, recorded from the reference's executor in tests/golden/ref_runs.npz (oracle/make_golden_refruns.py):
+# without a staged reference the oracle is held to the recording, with one to a live run that must equal it
+LOCK_STEP_CASES = [(0, 9), (0, 0), (1, 7), (2, 5), (3, 6), (4, 10), (5, 11), (6, 12), (7, 8)]
 
 
 def draws_for(q, rng, T, n):
@@ -28,21 +31,32 @@ def grid_actions(rng, T, n, da):
     return (rng.randint(-96, 97, size=(T, n, da)) / 64.0).astype(np.float32)
 
 
-@needs_ref
-@pytest.mark.parametrize("kind,mpl", [(0, 9), (0, 0), (1, 7), (2, 5), (3, 6), (4, 10), (5, 11), (6, 12), (7, 8)])
+def lock_step_inputs(kind):
+    from oracle import host_env as H
+    q = H.query(kind)
+    rng = np.random.RandomState(10 + kind)
+    T, n = 40, 6
+    return draws_for(q, rng, T, n), grid_actions(rng, T, n, q["act_dim"])
+
+
+def lock_step_reference(kind, mpl, draws, actions):
+    from oracle import ref_vecenv
+    return ref_vecenv.run(kind, mpl, actions, draws, scale_reward=0.25)
+
+
+@pytest.mark.parametrize("kind,mpl", LOCK_STEP_CASES)
 def test_oracle_lock_step_is_the_reference_executors(kind, mpl):
     """Bit for bit: observations (the RESET observation after a done), rewards (scale_reward a power of two: the
     product is exact), done flags of 40 lock steps of 6 env copies."""
+    from golden_util import ref_run
     from oracle import host_env as H
-    from oracle import ref_vecenv
     q = H.query(kind)
     lb, ub = H.action_bounds(kind)
     assert np.all(lb == np.round(lb)) and np.all(ub == np.round(ub)) and np.abs(ub - lb).max() < 1024
-    rng = np.random.RandomState(10 + kind)
-    T, n = 40, 6
-    draws = draws_for(q, rng, T, n)
-    actions = grid_actions(rng, T, n, q["act_dim"])
-    ref = ref_vecenv.run(kind, mpl, actions, draws, scale_reward=0.25)
+    draws, actions = lock_step_inputs(kind)
+    T, n = actions.shape[:2]
+    ref = ref_run("lock_step_k%d_m%d" % (kind, mpl),
+                  (lambda: lock_step_reference(kind, mpl, draws, actions)) if HAVE_REF else None)
     assert ref["modules"]["sandbox.rocky.tf.envs.vec_env_executor"] == "sandbox/rocky/tf/envs/vec_env_executor.py"
     assert ref["modules"]["rllab.envs.normalized_env"] == "rllab/envs/normalized_env.py"
     host = H.HostVecEnv(kind, n, max_path_length=mpl, normalize=True, scale_reward=0.25, auto_reset=True)

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_ref_vecenv import needs_ref
+from golden_util import ref_run
+from test_ref_vecenv import HAVE_REF
 
 
 def recording():
@@ -15,29 +16,42 @@ def recording():
     return d, np.arange(12.0).reshape(6, 2)
 
 
-@needs_ref
-@pytest.mark.parametrize("want,whole,steps,paths", [
+# (batch size asked for, whole_paths, lock steps the loop takes, paths it keeps as (env, t0, length)); the reference
+# loop's answers are recorded in tests/golden/ref_runs.npz (oracle/make_golden_refruns.py) and re-run live where the
+# reference is staged
+LOOP_CASES = [
     (2, True, 2, [(0, 0, 2)]),
     (3, True, 3, [(0, 0, 2), (1, 0, 3)]),
     (3, False, 3, [(0, 0, 2), (1, 0, 1)]),
     (6, True, 5, [(0, 0, 2), (1, 0, 3), (0, 2, 3)]),
     (6, False, 5, [(0, 0, 2), (1, 0, 3), (0, 2, 1)]),
     (11, True, 6, [(0, 0, 2), (1, 0, 3), (0, 2, 3), (1, 3, 3)]),
-])
-def test_reference_loop_on_a_replayed_recording(want, whole, steps, paths):
+]
+
+
+def loop_case_name(want, whole):
+    return "vec_sampler_loop_%d_%s" % (want, "whole" if whole else "cut")
+
+
+def loop_reference(want, whole):
     from oracle import ref_vecsampler
     d, r = recording()
-    out = ref_vecsampler.run(d, r, want, 100, whole)
+    return ref_vecsampler.run(d, r, want, 100, whole)
+
+
+@pytest.mark.parametrize("want,whole,steps,paths", LOOP_CASES)
+def test_reference_loop_on_a_replayed_recording(want, whole, steps, paths):
+    out = ref_run(loop_case_name(want, whole), (lambda: loop_reference(want, whole)) if HAVE_REF else None)
     assert int(out["steps"]) == steps
     assert list(zip(out["env"].tolist(), out["t0"].tolist(), out["length"].tolist())) == paths
 
 
-@needs_ref
 def test_reference_loop_refuses_a_recording_that_is_too_short():
-    from oracle import ref_vecsampler
-    d, r = recording()
-    with pytest.raises(RuntimeError, match="asks for lock step 6"):
-        ref_vecsampler.run(d, r, 12, 100, True)
+    rec = ref_run("vec_sampler_loop_too_short")        # what the reference's loop said, recorded
+    assert "asks for lock step 6" in str(rec["error"])
+    if HAVE_REF:
+        with pytest.raises(RuntimeError, match="asks for lock step 6"):
+            loop_reference(12, True)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
