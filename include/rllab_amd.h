@@ -397,6 +397,35 @@ int rl_lfb_normal_eq(size_t n_samples, int obs_dim, const float* obs, const int3
                      double* out, int variant, void* stream);   /* variant: 0 = matrix-core kernel (the library's choice),
                                                                  * 1 = register-blocked vector kernel (rl_launch_opts.lfb_valu) */
 
+/* ---- REPS: dual function and sample weights (rllab/algos/reps.py) ----------------------------------------------
+ * Planes as rl_path_scan leaves them: obs float[obs_dim][T][n] (obs_dim <= 30), rewards float[T][n], tin int32[T][n],
+ * dones / valid uint8[T][n].  Features (reps.py:207-211)  phi(o, t) = [clip(o, -10, 10), clip(o, -10, 10)^2, al, al^2,
+ * al^3, 1], al = t / 100, d = 2 * obs_dim + 4;  feature difference (:228-238)  fd_b = phi(next sample of b's path) - phi_b,
+ * the next sample of (t, i) being (t + 1, i) unless dones[t][i] is set, t == T - 1 or (t + 1, i) is invalid -- then the
+ * zero vector (the zero row the reference appends per path, :231);  delta_b = rewards_b + fd_b . v  (:102).  Sums and
+ * maximum run over the valid samples.  eta > 0;  v: d doubles in HOST memory, copied into the launch arguments. */
+
+/* Scratch (device bytes) for rl_reps_dual on a [T][n] batch; 0: bad arguments. */
+size_t rl_reps_workspace_bytes(int T, int n);
+
+/* out (device, d + 4 doubles) = [ m, S, S_delta, count, S_phi[d] ] at (eta, v):
+ *   m = max_b delta_b / eta,  S = sum_b e_b,  S_delta = sum_b e_b delta_b,  S_phi = sum_b e_b fd_b,  e_b = exp(delta_b / eta - m).
+ * The caller forms the dual of reps.py:174-184 and its gradient (:187) from them in float64:
+ *   g        = eta eps + eta log(S / count) + eta m + L2 (eta^2 + 1 / eta^2)
+ *   dg/dv    = S_phi / S
+ *   dg/d eta = eps + log(S / count) + m - S_delta / (eta S) + L2 (2 eta - 2 / eta^3).
+ * One read of the batch, float64 arithmetic, partial rows per workgroup folded in a fixed order by a second launch:
+ * two calls on the same input give bit-identical output. */
+int rl_reps_dual(int T, int n, int obs_dim, const float* obs, const float* rewards, const int32_t* tin,
+                 const uint8_t* dones, const uint8_t* valid, double eta, const double* v_host, void* workspace,
+                 size_t workspace_bytes, double* out, void* stream);
+
+/* weights float[T][n] = valid ? exp(delta / eta - m) : 0  (the per-sample factor of the policy loss, reps.py:110-112),
+ * m = dual_out[0] of a preceding rl_reps_dual call at the same (eta, v) on the same batch (device pointer). */
+int rl_reps_weights(int T, int n, int obs_dim, const float* obs, const float* rewards, const int32_t* tin,
+                    const uint8_t* dones, const uint8_t* valid, double eta, const double* v_host,
+                    const double* dual_out, float* weights, void* stream);
+
 /* One dense batch for the fused GaussianMLPPolicy update kernels.  Per-sample arrays
  * are planes with the sample axis last (B = n_samples). */
 typedef struct rl_policy_batch {

@@ -30,7 +30,7 @@ SYMBOLS = [
     "rl_discount_cumsum", "rl_debug_philox", "rl_policy_workspace_bytes", "rl_policy_activation_bytes", "rl_policy_loss_kl",
     "rl_policy_grad", "rl_policy_grad_loss", "rl_policy_fvp", "rl_policy_fvp_variant", "rl_policy_fvp_cg_step", "rl_cg_init", "rl_cg_step", "rl_trpo_step", "rl_line_search_point", "rl_line_search_decide", "rl_adam_step",
     "rl_path_scan", "rl_process_workspace_bytes", "rl_sample_stats_cols", "rl_sample_stats", "rl_adv_finish",
-    "rl_lfb_normal_eq",
+    "rl_lfb_normal_eq", "rl_reps_workspace_bytes", "rl_reps_dual", "rl_reps_weights",
     "rl_peer_mailbox_bytes", "rl_peer_alloc", "rl_peer_free", "rl_peer_export", "rl_peer_open", "rl_peer_close",
     "rl_peer_allreduce_sum",
     "rl_mlp_forward", "rl_mlp_forward_ws", "rl_mlp_backward", "rl_gaussian_head_workspace_bytes", "rl_gaussian_head", "rl_gaussian_fisher",
@@ -223,6 +223,10 @@ def _load():
     lib.rl_sample_stats.argtypes = [sz, vp, vp, vp, vp, vp, vp, f64, f64, vp, i32, vp, sz, vp, vp]
     lib.rl_adv_finish.argtypes = [sz, vp, vp, f64, f64, f64, vp, vp]
     lib.rl_lfb_normal_eq.argtypes = [sz, i32, vp, vp, vp, vp, vp, sz, vp, i32, vp]
+    lib.rl_reps_workspace_bytes.restype = sz
+    lib.rl_reps_workspace_bytes.argtypes = [i32, i32]
+    lib.rl_reps_dual.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, f64, vp, vp, sz, vp, vp]
+    lib.rl_reps_weights.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, f64, vp, vp, vp, vp]
     lib.rl_mlp_forward.argtypes = [pb, vp, vp, vp, vp]
     lib.rl_mlp_forward_ws.argtypes = [pb, vp, vp, sz, vp, vp, vp]
     lib.rl_mlp_backward.argtypes = [pb, vp, vp, sz, vp, vp]

@@ -52,7 +52,10 @@ class VPG(BatchPolopt, Serializable):
             def f_kl(inputs):  # noqa: F811  (HIP kernel version of the same statistic)
                 s = fused.loss_stats_host(inputs)      # the evaluation's one host read (shared with loss())
                 return s[1], s[3]
-        self.optimizer.update_opt(surr_obj, target=policy, inputs=None, fused=fused, weighted_mean_inputs=True)
+        # fused_loglik: surr_obj is the log-likelihood objective, not NPO's likelihood-ratio surrogate (LbfgsOptimizer asks
+        # the fused object for the matching value / gradient: ERWR; the other optimizers ignore the keyword)
+        self.optimizer.update_opt(surr_obj, target=policy, inputs=None, fused=fused, weighted_mean_inputs=True,
+                                  fused_loglik=True)
         self.opt_info = dict(f_kl=f_kl)
 
     def optimize_policy(self, itr, samples_data):

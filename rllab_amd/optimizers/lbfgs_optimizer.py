@@ -45,10 +45,15 @@ class LbfgsOptimizer(Serializable):
     def update_opt(self, loss, target, inputs=None, extra_inputs=None, gradients=None, *args, **kwargs):
         """``fused`` (keyword): an object with ``accepts(inputs)``, ``loss_and_kl(inputs)`` and
         ``value_and_grad(inputs, penalty)`` evaluating the same loss with HIP kernels
-        (regressors/fused_regressor_ops.py); the closure stays the definition and the fallback."""
+        (regressors/fused_regressor_ops.py); the closure stays the definition and the fallback.
+        ``fused_loglik`` (keyword, default False): ``loss`` is the log-likelihood objective -mean(logli * adv) of VPG /
+        ERWR (rllab/algos/vpg.py:91), so a policy's fused object is asked for ``loglik_loss(inputs)`` and
+        ``value_and_grad(inputs, vpg=True)`` -- its defaults evaluate the likelihood-ratio surrogate of NPO, a
+        different function away from the sampling parameters."""
         self._target = target
         self._loss = loss
         self._fused = kwargs.get("fused")
+        self._fused_loglik = bool(kwargs.get("fused_loglik", False))
 
     def _fused_for(self, inputs):
         f = getattr(self, "_fused", None)
@@ -57,6 +62,8 @@ class LbfgsOptimizer(Serializable):
     def loss(self, inputs, extra_inputs=None):
         inputs = tuple(inputs) + tuple(extra_inputs or ())
         if self._fused_for(inputs) is not None:
+            if getattr(self, "_fused_loglik", False):
+                return self._fused.loglik_loss(inputs)
             return self._fused.loss_and_kl(inputs)[0]
         with torch.no_grad():
             v = self._loss(self._target.flat_params, *inputs).to(torch.float64)
@@ -70,6 +77,8 @@ class LbfgsOptimizer(Serializable):
         def f_opt_wrapper(flat_params):
             self._target.set_param_values(flat_params, trainable=True)
             if fused is not None:
+                if getattr(self, "_fused_loglik", False):
+                    return fused.value_and_grad(inputs, vpg=True)
                 return fused.value_and_grad(inputs)
             return value_and_grad(self._loss, self._target, inputs)
 

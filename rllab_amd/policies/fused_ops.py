@@ -255,10 +255,14 @@ class FusedGaussianMLPOps(object):
             g.index_fill_(0, idx, 0.0)
         return g
 
-    def value_and_grad(self, inputs, penalty=0.0):
+    def value_and_grad(self, inputs, penalty=0.0, vpg=False):
         """float64 (value, flat gradient over the trainable parameters) of  surrogate loss + penalty * mean KL  in ONE
         pass (rl_policy_grad_loss with rl_policy_batch.kl_penalty): PenaltyLbfgsOptimizer's objective when PPO / NPO
-        run it on a GaussianMLPPolicy (rllab/algos/ppo.py:8-22, penalty_lbfgs_optimizer.py:66-79)."""
+        run it on a GaussianMLPPolicy (rllab/algos/ppo.py:8-22, penalty_lbfgs_optimizer.py:66-79).
+        ``vpg``: the log-likelihood objective  -sum_b w logp adv * inv_count  instead (rllab/algos/vpg.py:91; the
+        ``advantages`` slot may hold any per-sample factor: ERWR's shifted advantages, REPS's weights) -- what
+        LbfgsOptimizer minimises for VPG / ERWR / REPS.  No penalty term there."""
+        assert not (vpg and penalty), "the log-likelihood objective has no KL penalty"
         b, keep, inv = self._batch(inputs)
         dev = keep[0].device
         ws = self._workspace(dev)
@@ -268,8 +272,9 @@ class FusedGaussianMLPOps(object):
         b.activations = None
         b.kl_penalty = float(penalty)
         try:
-            _lib.check(_lib.lib.rl_policy_grad_loss(ctypes.byref(b), 0, _lib.ptr(ws), ws.numel(), _lib.ptr(grad),
-                                                    _lib.ptr(out4), _lib.stream_ptr()), "rl_policy_grad_loss")
+            _lib.check(_lib.lib.rl_policy_grad_loss(ctypes.byref(b), int(bool(vpg)), _lib.ptr(ws), ws.numel(),
+                                                    _lib.ptr(grad), _lib.ptr(out4), _lib.stream_ptr()),
+                       "rl_policy_grad_loss")
         finally:
             b.kl_penalty = 0.0
         packed = torch.cat([out4[:3], self.layout.unpack(grad)])
@@ -277,7 +282,14 @@ class FusedGaussianMLPOps(object):
         idx = self.policy._flat_index(trainable=True)
         host = packed.cpu().numpy()
         g = host[3:] if idx is None else host[3:][idx.cpu().numpy()]
+        if vpg:
+            return float(-host[2] * inv), g.copy()
         return float((-host[0] + penalty * host[1]) * inv), g.copy()
+
+    def loglik_loss(self, inputs):
+        """-sum_b w logp adv * inv_count at the current parameters (the value ``value_and_grad(vpg=True)`` differentiates):
+        third sum of the loss / KL pass, so it shares that pass and its one host read with ``loss_stats_host``."""
+        return -self.loss_stats_host(inputs)[2]
 
     def _fvp_into(self, b, ws, vec32, out, inputs=None):
         cached = inputs is not None and self._acts_tag is not None and self._acts_tag == self._eval_point(inputs)
