@@ -20,7 +20,10 @@ t + 1 = a reset after step t), exactly the table the GPU rollout was given.
 
     python oracle/ref_vecenv.py IN.npz OUT.npz
 IN : kind, max_path_length, actions [T, n, Da], reset_draws [T+1, R, n], scale_reward, normalize_obs, normalize_reward,
-     obs_alpha, reward_alpha, obs_mean0 / obs_var0 [n, Do], reward_mean0 / reward_var0 [n]  (estimates to resume from)
+     obs_alpha, reward_alpha, obs_mean0 / obs_var0 [n, Do], reward_mean0 / reward_var0 [n]  (estimates to resume from),
+     reset_at [k] lock steps BEFORE which the executor is ``reset()`` once more (the start of a further obtain_samples on
+     the same env copies: nothing but the reset itself is fresh); such a reset takes a slice of the table of its own, so
+     after r of them step t draws slice t + 1 + r, and obs[t] is then the reset's observation
 OUT: obs [T+1, n, Do] (slot 0 = reset(), slot t + 1 = what step t returned), rewards [T, n], dones [T, n],
      obs_mean / obs_var [n, Do], reward_mean / reward_var [n]  (every copy's estimates after the last step), modules
 """
@@ -108,8 +111,13 @@ def child_main(path_in, path_out):
     rew, done = np.zeros((T, n)), np.zeros((T, n), dtype=bool)
     clock["slice"] = 0
     obs[0] = np.asarray(vec.reset())
+    reset_at, extra = set(int(t) for t in z["reset_at"]), 0
     for t in range(T):
-        clock["slice"] = t + 1                      # a reset inside step t draws slice t + 1
+        if t in reset_at:
+            extra += 1
+            clock["slice"] = t + extra
+            obs[t] = np.asarray(vec.reset())
+        clock["slice"] = t + 1 + extra              # a reset inside step t draws slice t + 1 (+ the resets in between)
         o, r, d, _infos = vec.step(list(actions[t]))
         obs[t + 1], rew[t], done[t] = np.asarray(o), r, d
     np.savez(path_out, obs=obs, rewards=rew, dones=done,
@@ -121,7 +129,7 @@ def child_main(path_in, path_out):
 
 def run(kind, max_path_length, actions, reset_draws, scale_reward=1.0, normalize_obs=False, normalize_reward=False,
         obs_alpha=0.001, reward_alpha=0.001, obs_mean0=None, obs_var0=None, reward_mean0=None, reward_var0=None,
-        timeout=600):
+        timeout=600, reset_at=()):
     """Parent side: run the reference executor in a child process, return its arrays as a dict."""
     import numpy as np
     sys.path.insert(0, ROOT) if ROOT not in sys.path else None
@@ -133,7 +141,7 @@ def run(kind, max_path_length, actions, reset_draws, scale_reward=1.0, normalize
         np.savez(pin, kind=kind, max_path_length=max_path_length, actions=np.asarray(actions, np.float32),
                  reset_draws=np.asarray(reset_draws, np.float32), scale_reward=scale_reward,
                  normalize_obs=normalize_obs, normalize_reward=normalize_reward, obs_alpha=obs_alpha,
-                 reward_alpha=reward_alpha,
+                 reward_alpha=reward_alpha, reset_at=np.asarray(list(reset_at), np.int64),
                  obs_mean0=np.zeros((n, do)) if obs_mean0 is None else obs_mean0,
                  obs_var0=np.ones((n, do)) if obs_var0 is None else obs_var0,
                  reward_mean0=np.zeros(n) if reward_mean0 is None else reward_mean0,

@@ -147,9 +147,12 @@ class NormalizingVecEnv(object):
     Estimates start from the owning NormalizedEnv's (a snapshot's) and env copy 0's are written back to it when it
     is pickled or the executor terminates.  The (32,32) / (64,64) policies are sampled by the fused rollout, which feeds,
     applies and writes back the same estimate planes inside the kernel (``rollout``, rl_running_norm); every other policy
-    through ``reset`` / ``step`` below, one transition at a time."""
+    through ``reset`` / ``step`` below, one transition at a time.  Either way the estimates an ``obtain_samples`` leaves
+    behind are those of the lock steps in its batch: the reference's loop stops stepping where the batch ends."""
     graphable = False          # the sampler's hipGraph loop talks to the raw executor's buffers, not to step() below
-    stateful_rollouts = True   # a rollout advances the estimates for good: the sampler never launches one speculatively
+    # a rollout advances the estimates for good: the sampler never launches one speculatively, and takes a launch that
+    # ran past the end of its batch back to the cut (snapshot / restore)
+    stateful_rollouts = True
 
     def __init__(self, inner, scale_reward, normalize_obs, normalize_reward, obs_alpha, reward_alpha, owner=None):
         self.inner = inner
@@ -194,6 +197,21 @@ class NormalizingVecEnv(object):
         observation the previous launch left in the executor's buffer; no estimate is fed twice."""
         return self.inner.rollout(policy, horizon, reset_at_start=reset_at_start, norm=self,
                                   scale_reward=self.scale_reward_outer, **kwargs)
+
+    def snapshot(self):
+        """Everything a launch or a step advances -- the four estimate planes, the env state, the steps since the reset,
+        the carried observation and the RNG counter -- as copies ``restore`` puts back: the sampler takes a launch back
+        to the lock step its batch is cut at, so the estimates are fed exactly once per sampled transition."""
+        inner = self.inner
+        return (self.obs_mean.clone(), self.obs_var.clone(), self.reward_mean.clone(), self.reward_var.clone(),
+                inner.state.clone(), inner.ts.clone(), inner._obs.clone(), inner.step_counter)
+
+    def restore(self, snap):
+        inner = self.inner
+        for mine, saved in zip((self.obs_mean, self.obs_var, self.reward_mean, self.reward_var, inner.state, inner.ts,
+                                inner._obs), snap):
+            mine.copy_(saved)
+        inner.step_counter = snap[7]
 
     def write_back(self, env):
         """Env copy 0's estimates -> the NormalizedEnv that gets pickled (its ``_obs_mean`` / ``_obs_var`` state)."""

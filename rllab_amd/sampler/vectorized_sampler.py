@@ -9,15 +9,19 @@ at ``done`` or at ``max_path_length``, and the lock-step loop runs
 paths -- the batch holds at least ``batch_size`` samples in whole paths
 (rllab/algos/batch_polopt.py:23-34, rllab/sampler/parallel_sampler.py:98-126) and the
 paths still running when the loop stops are dropped.  With ``algo.whole_paths=False``
-every recorded step counts, running paths are kept as truncated paths and the batch
-is cut to exactly ``batch_size`` samples in path order (``truncate_paths``,
-parallel_sampler.py:129-155).  Here: one launch of ``max_path_length`` lock steps;
-for env kinds whose ``done`` is always False (Swimmer, HalfCheetah, DoublePendulum)
-that is ``n_envs * max_path_length`` samples in whole paths by construction and
-nothing is counted.  For env kinds that terminate, the finished samples per lock
-step are counted on the device, further launches WITHOUT a reset carry the same envs
-on until the count reaches ``batch_size`` (``_meet_batch_size``), and the batch is cut
-after the lock step at which the reference's loop would have stopped.
+that list -- the finished paths in the order they finished: by end lock step, then by
+env -- is cut from its end to exactly ``batch_size`` samples, the last kept path
+truncated (``truncate_paths``, parallel_sampler.py:129-155).  Here: one launch of
+``max_path_length`` lock steps; for env kinds whose ``done`` is always False (Swimmer,
+HalfCheetah, DoublePendulum) that is ``n_envs * max_path_length`` samples in whole paths
+by construction and nothing is counted.  For env kinds that terminate, the finished
+samples per lock step are counted on the device, further launches WITHOUT a reset carry
+the same envs on while paths keep finishing until the count reaches ``batch_size``
+(``_meet_batch_size``), and the batch is cut after the lock step at which the reference's
+loop would have stopped.  What outlives the batch -- NormalizedEnv's running estimates --
+is put back to that lock step too: a launch that ran past the cut is taken back and its
+kept steps are done again (``_commit_first_steps``), so the estimates are fed exactly once
+per sampled transition, as the reference's are.
 Differences that are the point of the rebuild: all ``n_envs`` copies advance in
 one HIP launch; with a fusable GaussianMLPPolicy the whole ``max_path_length``
 horizon (policy forward, action noise, env step, trajectory record, auto-reset)
@@ -107,6 +111,7 @@ class VectorizedSampler(BaseSampler):
         d.pop("_step_graph", None)
         d.pop("_prefetched", None)
         d.pop("_carry_obs", None)
+        d.pop("_launch_start", None)
         return d
 
     def _takes_fused_rollout(self, policy):
@@ -131,7 +136,8 @@ class VectorizedSampler(BaseSampler):
         executor's RNG counter goes back to where it was, so a run samples the same noise with or without the
         speculation.  An executor that carries state a dropped batch would have advanced for good -- NormalizedEnv's
         running estimates (``stateful_rollouts``) -- is never prefetched: the reference feeds each estimate exactly
-        once per sampled transition, and a snapshot taken after the prefetch would hold estimates one batch ahead.
+        once per sampled transition -- ``obtain_samples`` does too, taking back what a launch ran past the end of its
+        batch -- and a snapshot taken after the prefetch would hold estimates one batch ahead.
         ``BatchPolopt(prefetch_rollout=False)`` turns it off altogether."""
         policy = self.algo.policy
         pre = getattr(self, "_prefetched", None)
@@ -166,7 +172,7 @@ class VectorizedSampler(BaseSampler):
                 self._drop_prefetched()
         t_start = time.time()
         if first is None:
-            first = self._rollout_chunk(policy, algo.max_path_length, True)
+            first = self._launch(policy, algo.max_path_length, True)
         traj = self._meet_batch_size(policy, first)
         self.last_num_samples = traj.B
         self.last_sample_time = time.time() - t_start  # enqueue time only (+ the count read of a terminating env)
@@ -192,7 +198,39 @@ class VectorizedSampler(BaseSampler):
         return self._stepwise_rollout(policy, steps, first)
 
     # -- the batch-size contract ------------------------------------------------------------------------------------
-    MAX_EXTENSIONS = 64      # further launches before giving up on an env that never finishes a path
+    MAX_STALLED_CHUNKS = 8   # without a horizon: consecutive further launches in which no env ends a path, before giving up
+
+    def _launch(self, policy, steps, first):
+        """``_rollout_chunk`` of ``obtain_samples``: an executor whose rollouts advance state for good (NormalizedEnv's
+        running estimates, ``stateful_rollouts``) is snapshotted first, so that the launch can be taken back to the
+        lock step the batch is cut at (``_commit_first_steps``)."""
+        v = self.vec_env
+        self._launch_start = None
+        if getattr(v, "stateful_rollouts", False):
+            self._launch_start = (v.snapshot(), getattr(self, "_carry_obs", None), bool(first))
+        return self._rollout_chunk(policy, steps, first)
+
+    def _commit_first_steps(self, policy, chunk, steps):
+        """The newest launch recorded ``chunk`` and the batch keeps its first ``steps`` lock steps only: put the executor
+        where the reference's loop leaves it, which stops stepping -- and feeding the running estimates -- at that lock
+        step.  The executor goes back to the snapshot taken before the launch and does the kept steps again: the fused
+        rollout is a pure function of (seed, env, step counter) and reproduces them bit for bit; a per-transition loop
+        steps the envs through the actions ``chunk`` recorded, without asking the policy again."""
+        start = getattr(self, "_launch_start", None)
+        if start is None:
+            return
+        v = self.vec_env
+        snap, carry, first = start
+        v.restore(snap)
+        self._carry_obs = carry
+        self._launch_start = None
+        if self._takes_fused_rollout(policy):
+            self._rollout_chunk(policy, steps, first)
+            return
+        obs = v.reset() if first else carry
+        for t in range(steps):
+            obs = v.step(chunk.actions[:, t, :].t())[0]
+        self._carry_obs = obs
 
     def _path_index(self, traj):
         """(tin int32 [T, N] step index inside its path, valid bool [T, N] sample of a path that ends in the batch)."""
@@ -203,22 +241,33 @@ class VectorizedSampler(BaseSampler):
                                          None, _lib.stream_ptr()), "rl_path_scan")
         return tin, valid.view(torch.bool)
 
-    def _finished_by_step(self, traj):
+    def _finished_by_step(self, traj, carry=None):
         """[T] int64 on the device: samples in the paths that ended at or before lock step t -- ``n_samples`` of the
-        reference's loop after that step (vectorized_sampler.py:55,98-99)."""
-        tin, _ = self._path_index(traj)
-        ended = (tin.to(torch.int64) + 1) * traj.dones.to(torch.int64)
-        return torch.cumsum(ended.sum(dim=1), 0)
+        reference's loop after that step (vectorized_sampler.py:55,98-99).  ``carry`` [N] int64: ``traj`` is a further
+        launch on the same envs and env i's running path was ``carry[i]`` steps long when it began; updated in place
+        to the lengths of the paths running when ``traj`` ends, so only the new lock steps are ever scanned."""
+        tin = self._path_index(traj)[0].to(torch.int64)
+        done = traj.dones.to(torch.int64)
+        if carry is not None:
+            t_idx = torch.arange(traj.T, device=traj.device).unsqueeze(1)
+            tin = tin + (tin == t_idx).to(torch.int64) * carry.unsqueeze(0)     # paths that began before this launch
+            carry.copy_((tin[-1] + 1) * (1 - done[-1]))
+        return torch.cumsum(((tin + 1) * done).sum(dim=1), 0)
 
     def _meet_batch_size(self, policy, first):
         """Carry the envs of ``first`` (``max_path_length`` lock steps from a reset) on until the batch holds
         ``algo.batch_size`` samples in finished paths, and cut it after the lock step at which the reference's loop
-        stops.  ``algo.whole_paths=False``: the first ``batch_size`` of those samples in path order (env by env), the
-        last kept path truncated -- what ``truncate_paths`` leaves of the list (batch_polopt.py:30-34).
+        stops.  An executor with running estimates is left as that loop leaves it: fed by the kept lock steps and no
+        more (``_commit_first_steps``).  ``algo.whole_paths=False``: the first ``batch_size`` of those samples with the
+        paths in the order the reference lists them -- by the lock step a path ends at, then by env -- and the last kept
+        path truncated: what ``truncate_paths`` leaves of the list (batch_polopt.py:30-34).
+        Each further launch is scanned on its own (one blocking read of its [steps] counts) and sized from the
+        shortfall; the loop goes on while paths keep finishing, as the reference's does.
         Sharded over ranks (each with ``n_envs`` envs and ``batch_size`` samples of the job's world x batch_size): the
-        count is the sum over the shards -- one sum all-reduce of the [T] per-step counts per look, for env kinds that
-        terminate -- so every rank carries on by the same number of lock steps and cuts at the same one, and the job
-        samples exactly what one process with all the envs would."""
+        count is the sum over the shards -- one sum all-reduce of the per-step counts per launch, for env kinds that
+        terminate -- so every rank carries on by the same number of lock steps and cuts at the same one, paths are
+        ordered by (end lock step, global env index) across the shards, and the job samples exactly what one process
+        with all the envs would."""
         algo, v = self.algo, self.vec_env
         world, rank = D.world_size(), D.rank()
         want, N, T = int(algo.batch_size) * world, first.N * world, int(algo.max_path_length)
@@ -228,45 +277,80 @@ class VectorizedSampler(BaseSampler):
             # (nothing to count, nothing read back: the launch stays asynchronous)
             rounds = max(1, -(-want // (N * T)))
             for _ in range(rounds - 1):
-                chunks.append(self._rollout_chunk(policy, T, False))
+                chunks.append(self._launch(policy, T, False))
             traj = Trajectories.concat(chunks)
             if not algo.whole_paths and N * traj.T > want:
-                self._keep_first(traj, want - rank * traj.B, None)
+                self._keep_first(traj, want, None, env0=rank * first.N, n_all=N)
             return traj
-        for _ in range(self.MAX_EXTENSIONS):
-            traj = Trajectories.concat(chunks)
-            chunks = [traj]
-            finished = D.all_reduce_sum_(self._finished_by_step(traj)).cpu()   # the one host read of such a batch
+        carry = torch.zeros(first.N, dtype=torch.int64, device=first.device)
+        count = stalled_chunks = stalled_steps = 0
+        while True:
+            new = chunks[-1]
+            finished = D.all_reduce_sum_(self._finished_by_step(new, carry)).cpu() + count   # the one host read per launch
             hit = torch.nonzero(finished >= want)
             if hit.numel() > 0:
-                traj = traj.first_steps(int(hit[0]) + 1)
-                if not algo.whole_paths and int(finished[int(hit[0])]) > want:
-                    whole = self._path_index(traj)[1]
-                    mine = whole.sum().reshape(1)
-                    before = int(D.all_gather_rows(mine)[:rank].sum()) if world > 1 else 0   # path order: rank by rank
-                    self._keep_first(traj, want - before, whole)
+                keep = int(hit[0]) + 1
+                if keep < new.T:
+                    self._commit_first_steps(policy, new, keep)
+                    chunks[-1] = new.first_steps(keep)
+                traj = Trajectories.concat(chunks)
+                if not algo.whole_paths and int(finished[keep - 1]) > want:
+                    self._keep_first(traj, want, self._path_index(traj)[1], env0=rank * first.N, n_all=N)
                 return traj
-            short = want - int(finished[-1])
-            # paths still running are finished by the continuation and count then; aim a little past the shortfall
-            k = max(8, -(-3 * short // (2 * N)))
-            chunks.append(self._rollout_chunk(policy, min(k, T) if T > 0 else k, False))
-        raise RuntimeError("VectorizedSampler: %d samples in finished paths after %d further launches, batch_size is %d "
-                           "(an env that never ends a path, and no max_path_length?)"
-                           % (int(finished[-1]), self.MAX_EXTENSIONS, want))
+            gained, count = int(finished[-1]) - count, int(finished[-1])
+            stalled_chunks, stalled_steps = (0, 0) if gained > 0 else (stalled_chunks + 1, stalled_steps + new.T)
+            if (stalled_steps >= T) if T > 0 else (stalled_chunks >= self.MAX_STALLED_CHUNKS):
+                raise RuntimeError("VectorizedSampler: no env has ended a path in the last %d lock steps (%d launches); %d "
+                                   "samples are in finished paths, batch_size is %d (%s)"
+                                   % (stalled_steps, stalled_chunks, count, want,
+                                      "the executor does not end paths at max_path_length = %d" % T if T > 0 else
+                                      "no max_path_length, and the env's done never fires"))
+            short = want - count
+            # paths still running are finished by the continuation and count then; aim a little past the shortfall, in
+            # launches of at most one horizon unless a whole round of the envs cannot cover it; twice as far each time
+            # nothing finished
+            k = max(8, -(-3 * short // (2 * N))) << stalled_chunks
+            if T > 0 and short <= N * T:
+                k = min(k, T)
+            chunks.append(self._launch(policy, k, False))
 
     @staticmethod
-    def _keep_first(traj, want, whole):
-        """``traj.valid`` <- the first ``want`` samples of the finished paths in path order (env by env, then time);
-        the sample the cut falls on ends its path (``truncate_paths``, parallel_sampler.py:129-155).  ``whole``
-        [T, N] bool: samples of paths that end in the batch (None: all of them)."""
+    def _keep_first(traj, want, whole, step_base=None, env0=0, n_all=None):
+        """``traj.valid`` <- the first ``want`` samples of the finished paths, the paths in the order the reference's
+        loop appends them -- by the lock step they end at, then by env (vectorized_sampler.py:72-97) -- and time inside
+        a path; the sample the cut falls on ends its path (``truncate_paths``, parallel_sampler.py:129-155).  ``whole``
+        [T, N] bool: samples of paths that end in the batch; None: an env kind that never terminates, whose paths are
+        the rounds of ``max_path_length`` lock steps.  Sharded: this shard's envs are ``env0 ...`` of ``n_all``, and the
+        samples of the other shards' paths that are listed before this shard's are counted in (one all-gather of the
+        per-step counts)."""
         T, N = traj.T, traj.N
         dev = traj.device
-        want = max(0, min(int(want), T * N))      # (a shard behind the cut keeps nothing, one before it everything)
+        n_all = N if n_all is None else int(n_all)
+        t_idx = torch.arange(T, device=dev).unsqueeze(1)
+        env = torch.arange(N, device=dev).unsqueeze(0)
         if whole is None:
-            rank = (torch.arange(N, device=dev).unsqueeze(0) * T + torch.arange(T, device=dev).unsqueeze(1)) + 1
+            L = int(traj.max_path_length) if int(traj.max_path_length) > 0 else T
+            rank = (t_idx // L) * (n_all * L) + (env0 + env) * L + t_idx % L + 1
             keep = rank <= want
         else:
-            rank = torch.cumsum(whole.t().reshape(-1).to(torch.int64), 0).reshape(N, T).t()   # 1-based, env-major
+            done = traj.dones.bool() & whole
+            tin = traj.time_in_path()
+            ended = (tin + 1) * done                                  # [T, N] length of the path that ends here
+            rows = ended.sum(dim=1)
+            if step_base is None:
+                if n_all > N:
+                    every = D.all_gather_rows(rows)                   # [world, T]: rank r's samples in paths ending at t
+                    mine = env0 // N
+                    total = every.sum(dim=0)
+                    step_base = torch.cumsum(total, 0) - total + every[:mine].sum(dim=0)
+                else:
+                    step_base = torch.cumsum(rows, 0) - rows
+            # samples listed before the path that ends at (t, env) ...
+            before = step_base.unsqueeze(1) + torch.cumsum(ended, 1) - ended
+            # ... handed to every sample of that path: the first done at or after t in its column
+            end_t = torch.where(done, t_idx.expand(T, N), torch.full((T, N), T - 1, dtype=torch.int64, device=dev))
+            end_t = torch.flip(torch.cummin(torch.flip(end_t, [0]), 0).values, [0])
+            rank = before.gather(0, end_t) + tin + 1
             keep = whole & (rank <= want)
         traj.valid = keep.contiguous()
         traj.dones[keep & (rank == want)] = 1

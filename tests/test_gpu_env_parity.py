@@ -186,7 +186,11 @@ def _ref_scan(x, c):
     return y
 
 
-@pytest.mark.parametrize("T,n", [(1, 1), (7, 3), (100, 257), (500, 1000), (513, 64)])
+# (37, 32801) / (512, 32768): (n + 31) / 32 >= 1024 workgroups, the 32-envs-per-workgroup instantiation -- a partial last
+# workgroup; a full chunk grid whose workgroup count is a multiple of 8 (the XCD remap).  (1024, 40) / (1025, 40): horizons
+# beyond the register kernels', the fall-through to gae_kernel.
+@pytest.mark.parametrize("T,n", [(1, 1), (7, 3), (100, 257), (500, 1000), (513, 64), (37, 32801), (512, 32768),
+                                 (1024, 40), (1025, 40)])
 def test_gae_kernel_vs_float64_loop(T, n):
     from rllab_amd import _lib
     rng = np.random.RandomState(T * 1000 + n)
@@ -197,9 +201,10 @@ def test_gae_kernel_vs_float64_loop(T, n):
     gamma, lam = 0.99, 0.97
     adv = torch.empty((T, n), dtype=torch.float32, device=dev)
     ret = torch.empty((T, n), dtype=torch.float32, device=dev)
+    und = torch.empty((T, n), dtype=torch.float32, device=dev)
     tr, tv, td = (torch.as_tensor(x, device=dev) for x in (r, v, done))
     _lib.check(_lib.lib.rl_gae(T, n, _lib.ptr(tr), _lib.ptr(tv), _lib.ptr(td), gamma, lam, _lib.ptr(adv),
-                               _lib.ptr(ret), None, _lib.stream_ptr()))
+                               _lib.ptr(ret), _lib.ptr(und), _lib.stream_ptr()))
     end = done.astype(bool).copy()
     end[-1] = True
     keep = 1.0 - end
@@ -210,6 +215,8 @@ def test_gae_kernel_vs_float64_loop(T, n):
     scale = max(1.0, np.abs(want_adv).max())
     assert np.abs(adv.cpu().numpy() - want_adv).max() <= 1e-5 * scale
     assert np.abs(ret.cpu().numpy() - want_ret).max() <= 1e-5 * max(1.0, np.abs(want_ret).max())
+    want_und = _ref_scan(r.astype(np.float64), keep)                   # the undiscounted return-to-go of the path
+    assert np.abs(und.cpu().numpy() - want_und).max() <= 1e-5 * max(1.0, np.abs(want_und).max())
     # values=None path
     _lib.check(_lib.lib.rl_gae(T, n, _lib.ptr(tr), None, _lib.ptr(td), gamma, 1.0, _lib.ptr(adv),
                                _lib.ptr(ret), None, _lib.stream_ptr()))
@@ -225,6 +232,25 @@ def test_discount_cumsum_special():
     x = rng.randn(500, 33)
     want = _ref_scan(x, np.full_like(x, 0.99))
     assert np.abs(special.discount_cumsum(x, 0.99) - want).max() <= 1e-5 * np.abs(want).max()
+
+
+@pytest.mark.parametrize("T,n", [(1, 1), (33, 5), (500, 33), (513, 100)])
+def test_discount_cumsum_with_dones_vs_float64_loop(T, n):
+    """``dones`` end a path inside a column: y[t] = x[t] + discount * (1 - done[t]) * y[t+1]; [T, n] tensors on the
+    device, [T, n] numpy arrays and the 1-D numpy form."""
+    from rllab_amd.misc import special
+    rng = np.random.RandomState(T * 1000 + n)
+    x = rng.randn(T, n)
+    done = (rng.rand(T, n) < 0.1).astype(np.uint8)
+    want = _ref_scan(x.astype(np.float32).astype(np.float64), 0.97 * (1.0 - done))
+    tol = 1e-5 * max(1.0, np.abs(want).max())
+    got = special.discount_cumsum(x, 0.97, dones=done)
+    assert got.shape == (T, n) and got.dtype == np.float64 and np.abs(got - want).max() <= tol
+    got = special.discount_cumsum(torch.as_tensor(x, dtype=torch.float32, device=_dev()), 0.97,
+                                  dones=torch.as_tensor(done, device=_dev()))
+    assert np.abs(got.cpu().numpy() - want).max() <= tol
+    got = special.discount_cumsum(x[:, 0], 0.97, dones=done[:, 0].astype(bool))
+    assert got.shape == (T,) and np.abs(got - want[:, 0]).max() <= tol
 
 
 def test_smoke_entry():

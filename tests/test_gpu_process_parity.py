@@ -244,19 +244,17 @@ def test_cartpole_whole_paths_drop_incomplete_tails(quiet_logger):
 
 
 def _np_tin_valid(done, whole_paths=True):
+    """Step index inside its path and "a done flag at or after it in its column", all columns at once (row loops)."""
     T, n = done.shape
+    done = done.astype(bool)
     tin = np.zeros((T, n), np.int64)
     valid = np.zeros((T, n), bool)
-    for i in range(n):
-        start = 0
-        for t in range(T):
-            if t > 0 and done[t - 1, i]:
-                start = t
-            tin[t, i] = t - start
-        seen = False
-        for t in range(T - 1, -1, -1):
-            seen = seen or bool(done[t, i])
-            valid[t, i] = seen or not whole_paths
+    for t in range(1, T):
+        tin[t] = np.where(done[t - 1], 0, tin[t - 1] + 1)
+    seen = np.zeros(n, bool)
+    for t in range(T - 1, -1, -1):
+        seen = seen | done[t]
+        valid[t] = seen | (not whole_paths)
     return tin, valid
 
 
@@ -267,7 +265,9 @@ def _np_features(obs, tin):
     return np.concatenate([o, o ** 2, al, al ** 2, al ** 3, np.ones_like(al)], axis=1)
 
 
-@pytest.mark.parametrize("T,n,do", [(1, 1, 4), (7, 3, 6), (100, 257, 13), (513, 64, 20)])
+# (37, 32801, 4): (n + 31) / 32 >= 1024 workgroups, path_scan_reg_kernel<16, 32> with a partial last workgroup;
+# (1025, 40, 6): a horizon beyond the register kernels'
+@pytest.mark.parametrize("T,n,do", [(1, 1, 4), (7, 3, 6), (100, 257, 13), (513, 64, 20), (37, 32801, 4), (1025, 40, 6)])
 @pytest.mark.parametrize("whole_paths", [True, False])
 @pytest.mark.parametrize("valu_form", [False, True])
 def test_path_scan_and_normal_equations_vs_numpy(T, n, do, whole_paths, valu_form, monkeypatch):

@@ -165,12 +165,22 @@ def _fused_setup(name, flags, epw, monkeypatch, T, n=37, mpl=9):
     return env, pol, v, eps, draws, est0
 
 
-def _check_fused_against_reference(name, v, traj, draws, est0, mpl):
+def _check_fused_against_reference(name, v, traj, draws, est0, mpl, min_dones=None, before=None):
+    """``min_dones``: how many paths the batch must at least end (default: one per env).  ``before`` (actions [T0, n, Da],
+    draws [T0 + 1, R, n]): the executor sampled that batch from ``est0`` first and ``traj`` after a reset of its own; the
+    reference's executor does the same on the same env copies (a Box2D world keeps its warm-start impulses over a reset)
+    and is compared from that reset on."""
     from oracle import ref_vecenv
     tol = 5e-4 if name in ("cheetah", "walker", "hopper") else 5e-5
     T, n = traj.T, traj.N
     actions = traj.actions.permute(1, 2, 0).cpu().numpy()                     # [T, n, Da] as the policy sampled them
-    ref = ref_vecenv.run(v.kind, mpl, actions, draws, scale_reward=0.25, **(est0 or {}))
+    if before is None:
+        ref = ref_vecenv.run(v.kind, mpl, actions, draws, scale_reward=0.25, **(est0 or {}))
+    else:
+        T0 = before[0].shape[0]
+        ref = ref_vecenv.run(v.kind, mpl, np.concatenate([before[0], actions]), np.concatenate([before[1], draws]),
+                             scale_reward=0.25, reset_at=[T0], **(est0 or {}))
+        ref.update(dones=ref["dones"][T0:], rewards=ref["rewards"][T0:], obs=ref["obs"][T0:])
     assert np.array_equal(traj.dones.cpu().numpy().astype(bool), ref["dones"])
     ok, err = close(traj.obs.permute(1, 2, 0).cpu().numpy(), ref["obs"][:T], tol)   # obs[t]: what action t was computed from
     assert ok, err
@@ -188,7 +198,7 @@ def _check_fused_against_reference(name, v, traj, draws, est0, mpl):
         assert ok, err
         ok, err = close(v.reward_var.cpu().numpy(), ref["reward_var"], tol)
         assert ok, err
-    assert int(ref["dones"].sum()) >= n
+    assert int(ref["dones"].sum()) >= (n if min_dones is None else min_dones)
     return ref
 
 
