@@ -326,6 +326,56 @@ int rl_rollout_plan_query(const rl_rollout_args* args, rl_rollout_plan* plan);
 int rl_rollout_lds_bytes(int env_kind, int hidden0, int hidden1, int hidden2, int std_hidden0, int std_hidden1,
                          int std_hidden2, size_t* bytes, size_t* limit);
 
+/* Population rollout: the fused rollout with ONE PARAMETER VECTOR PER ENV.  Evaluates n_cand candidate policies, n_evals
+ * rollouts each, in one launch -- the inner loop of the cross-entropy method (rllab/algos/cem.py:29-56, _worker_rollout_policy:
+ * set_param_values(a candidate), rollout(env, policy, max_path_length), discounted and undiscounted return of the path) for
+ * the whole population at once.  Env i (n_envs = n_cand * n_evals) runs candidate i % n_cand, evaluation i / n_cand: it is
+ * reset, then stepped `horizon` times with auto-reset exactly as rl_rollout_gaussian_mlp steps it (same Philox streams:
+ * reset, policy noise, action noise, observation noise keyed by (seed, env_offset + i, step_counter + t)), its action mean
+ * coming from its own candidate's tanh MLP evaluated per lane in float32 (rollout_population_kernel<Env, H>,
+ * csrc/population_kernels.hip).  theta_pop_T is the population TRANSPOSED: row p holds entry p of every candidate, the
+ * entries in the order of rl_rollout_args.theta for hidden sizes (hidden, hidden).
+ * first_path[3][n]: of every env's FIRST path (up to its first done, the forced one at max_path_length included; the whole
+ * horizon when there is none) the discounted return sum_t discount^t r_t, the undiscounted return, and the length, all
+ * float32 accumulated in float32 (discount^t in float64) over the rewards as recorded (scale_reward applied).
+ * Every recording plane may be NULL = not stored; with all five NULL an evaluation writes 12 bytes per env.
+ * layer_activations: 0 (tanh, tanh), or tanh + identity -- the kernel copy of a ONE-hidden-layer policy, W1 = I (as
+ * rl_rollout_args.layer_activations); anything else, and any hidden size but 32 / 64, is RL_ERR_UNSUPPORTED. */
+typedef struct rl_population_args {
+    int32_t kind;             /* rl_env_kind */
+    int32_t n_cand;           /* candidates: columns of theta_pop_T */
+    int32_t n_evals;          /* rollouts per candidate; n_envs = n_cand * n_evals */
+    int32_t horizon;          /* T: steps per env in this call */
+    int32_t max_path_length;  /* forced done when ts reaches it */
+    int32_t normalize;        /* NormalizedEnv action map on/off */
+    int32_t hidden;           /* 32 or 64: both hidden layers (narrower layers: zero padding, exact) */
+    int32_t layer_activations;
+    int32_t env_offset;       /* global index of env 0 (RNG key) */
+    float scale_reward;
+    float log_min_std;        /* log_std floor per candidate, log(min_std) */
+    int32_t reserved_pad;
+    double discount;
+    uint64_t seed;
+    uint64_t step_counter;    /* global step index of t = 0 (RNG counter base) */
+    float* state;             /* float[state_dim][n]  in/out (persisted solver state survives the reset) */
+    int32_t* ts;              /* int32[n]             out */
+    const float* theta_pop_T; /* float[P_pad][n_cand]: W0[do][H], b0, W1[H][H], b1, Wout[H][da], bout, log_std per column */
+    const float* eps;         /* NULL or float[act_dim][T][n] injected N(0,1) policy noise */
+    const float* reset_draws; /* NULL or float[T+1][reset_draws][n]: slice 0 = initial reset, slice t+1 = reset after step t */
+    const float* act_noise_z; /* NULL or float[T][act_dim][n] injected draws of the env's action noise */
+    const float* obs_noise_z; /* NULL or float[T+1][obs_dim][n] injected draws of the env's observation noise */
+    float* obs;               /* NULL or float[obs_dim][T][n] */
+    float* actions;           /* NULL or float[act_dim][T][n] */
+    float* means;             /* NULL or float[act_dim][T][n] */
+    float* rewards;           /* NULL or float[T][n] */
+    uint8_t* dones;           /* NULL or uint8[T][n] */
+    float* first_path;        /* float[3][n]: discounted return, undiscounted return, length of the first path */
+    const rl_env_cfg* cfg;    /* host; NULL = the env's defaults (its action_noise_z / obs_noise_z are not read here) */
+    const rl_launch_opts* opts;   /* host; NULL.  Reserved: the launch has one shape, 64 envs per single-wavefront workgroup */
+} rl_population_args;
+
+int rl_rollout_population(const rl_population_args* args, void* stream);
+
 /* Segmented reverse linear-recurrence scans over [T][n] planes, fused:
  *   delta[t] = r[t] + gamma * V[t+1] * (1 - end[t]) - V[t]
  *   adv[t]   = delta[t] + gamma*lambda * (1 - end[t]) * adv[t+1]

@@ -310,6 +310,72 @@ class HipVecEnv(object):
         return Trajectories(obs, act, mean, policy.recorded_log_std(), rew, done,
                             self.max_path_length, log_std_planes=log_stds)
 
+    # -- population rollout: one parameter vector per env ---------------------------
+    def rollout_population(self, theta_pop, n_evals, horizon, discount, record=True, eps=None, reset_draws=None,
+                           action_noise_z=None, obs_noise_z=None, layer_activations=0, log_min_std=None):
+        """Evaluate a population of policies in ONE launch (rl_rollout_population; the inner loop of CEM,
+        rllab/algos/cem.py:29-56).  ``theta_pop``: [n_cand, P_pad] float32 device tensor, one candidate per row in the
+        kernels' layout for hidden sizes (H, H), H = 32 or 64 (``KernelLayout.pack_rows``); this executor must hold
+        ``n_cand * n_evals`` envs, env i runs candidate ``i % n_cand``, evaluation ``i // n_cand``.  Every env is reset and
+        stepped ``horizon`` times with auto-reset.  Returns ``(Trajectories or None, first_path)``: the recorded planes
+        (``record=False``: nothing but ``first_path`` is stored) and ``first_path`` [3, n] = discounted return under
+        ``discount``, undiscounted return and length of every env's first path.  The batch carries every env's own log_std as
+        ``log_std_planes`` (a [Da, 1, n] row broadcast over T, no copy).  ``layer_activations``: as ``KernelLayout.layer_activations``
+        (tanh layers, or the identity second layer of a one-hidden-layer policy); ``log_min_std``: the floor of log_std
+        (log(policy.min_std); None = no floor).  The injected planes are those of ``rollout`` (parity runs)."""
+        if self.position_ids is not None:
+            raise NotImplementedError("rollout_population on position_only observations: the candidates' first layers are "
+                                      "built on the kept rows")
+        T, n = int(horizon), self.n
+        do, da = self.q["obs_dim"], self.q["act_dim"]
+        assert torch.is_tensor(theta_pop) and theta_pop.is_cuda and theta_pop.dtype == torch.float32 and theta_pop.dim() == 2
+        n_cand, p_pad = int(theta_pop.shape[0]), int(theta_pop.shape[1])
+        if n_cand * int(n_evals) != n:
+            raise ValueError("rollout_population: %d candidates x %d evaluations on an executor of %d envs" % (
+                n_cand, int(n_evals), n))
+        hidden = [H for H in (32, 64) if do * H + H + H * H + H + H * da + 2 * da == p_pad]
+        if not hidden:
+            raise NotImplementedError("rollout_population: rows of %d parameters are no (32, 32) / (64, 64) policy on this env "
+                                      "(KernelLayout.pack_rows makes them)" % p_pad)
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        theta_T = theta_pop.t().contiguous()                      # [P_pad, n_cand]: lane i reads column i % n_cand
+        obs = act = mean = rew = done = None
+        if record:
+            obs = torch.empty((do, T, n), **f32)
+            act = torch.empty((da, T, n), **f32)
+            mean = torch.empty((da, T, n), **f32)
+            rew = torch.empty((T, n), **f32)
+            done = torch.empty((T, n), dtype=torch.uint8, device=dev)
+        first_path = torch.empty((3, n), **f32)
+        eps = self._plane(eps, (da, T, n))
+        reset_draws = self._plane(reset_draws, (T + 1, self.q["reset_draws"], n))
+        az = self._plane(action_noise_z, (T, da, n))
+        oz = self._plane(obs_noise_z, (T + 1, do, n))
+        lms = -1e30 if log_min_std is None else float(log_min_std)
+        self._cfg_with(None, None)
+        args = _lib.PopulationArgs(
+            kind=self.kind, n_cand=n_cand, n_evals=int(n_evals), horizon=T, max_path_length=self.max_path_length,
+            normalize=int(self.normalize), hidden=hidden[0], layer_activations=int(layer_activations),
+            env_offset=self.env_offset, scale_reward=self.scale_reward, log_min_std=lms, discount=float(discount),
+            seed=self.seed, step_counter=self.step_counter,
+            state=self.state.data_ptr(), ts=self.ts.data_ptr(), theta_pop_T=theta_T.data_ptr(),
+            eps=None if eps is None else eps.data_ptr(),
+            reset_draws=None if reset_draws is None else reset_draws.data_ptr(),
+            act_noise_z=None if az is None else az.data_ptr(), obs_noise_z=None if oz is None else oz.data_ptr(),
+            obs=None if obs is None else obs.data_ptr(), actions=None if act is None else act.data_ptr(),
+            means=None if mean is None else mean.data_ptr(), rewards=None if rew is None else rew.data_ptr(),
+            dones=None if done is None else done.data_ptr(), first_path=first_path.data_ptr(),
+            cfg=ctypes.pointer(self.cfg), opts=_lib.launch_opts())
+        _lib.check(_lib.lib.rl_rollout_population(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_population")
+        self.step_counter += T + 1            # as rollout(): counter T belongs to the reset after the last step
+        if not record:
+            return None, first_path
+        # every env's own (floored) log_std row, broadcast over time: what PathList / policy.log_diagnostics read
+        ls = theta_pop[:, p_pad - da:].clamp_min(lms).t().repeat(1, int(n_evals))            # [Da, n]
+        planes = ls.unsqueeze(1).expand(da, T, n)
+        return Trajectories(obs, act, mean, None, rew, done, self.max_path_length, log_std_planes=planes), first_path
+
 
 class HipEnv(Env, Serializable):
     """Base of the HIP-native envs; subclasses set ``KIND``."""

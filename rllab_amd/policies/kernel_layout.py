@@ -230,6 +230,21 @@ class KernelLayout(object):
         out.index_copy_(0, self.index, vec)
         return out
 
+    def pack_rows(self, xs):
+        """Real-layout parameter ROWS [n, P] -> kernel-layout rows [n, P_pad], each row what ``theta()`` would hold with that
+        row as the policy's parameters: zeros at the padded positions, and the constant W1 = I of the identity second
+        layer a one-hidden-layer policy carries.  Same dtype and device as ``xs`` (a population of candidates:
+        ``HipVecEnv.rollout_population``)."""
+        if self.exact:
+            return xs
+        out = torch.zeros((xs.shape[0], self.P_pad), dtype=xs.dtype, device=xs.device)
+        if self.identity_layer:
+            H = self.H
+            ones = self.policy.obs_dim * H + H + torch.arange(H, device=xs.device) * (H + 1)
+            out[:, ones] = 1.0
+        out.index_copy_(1, self.index.to(xs.device), xs)
+        return out
+
     def unpack(self, vec_pad):
         """Kernel-layout vector [P_pad] -> real layout [P]."""
         if self.exact:
