@@ -627,6 +627,56 @@ int rl_gaussian_fisher(size_t n_samples, int act_dim, const float* dmean, const 
                        const float* weights, float inv_count, float log_min_std, float* g_mean, float* g_log_std,
                        void* stream);
 
+/* ---- discrete actions: GridWorld rollout and the categorical head (csrc/categorical_kernels.hip) -------------------
+ * rllab/envs/grid_world_env.py:36-149 sampled by a rllab/policies/categorical_mlp_policy.py:15-85.  Observations are
+ * one-hot, so the policy is a function of the state index alone: the rollout reads a probability table the caller
+ * builds once per parameter version (rl_mlp_forward_ws on the identity observation planes, rl_categorical_softmax).
+ * One lane per env, the whole horizon in one launch.  Per env and step: record the one-hot observation; one uniform
+ * (Philox keyed by seed, env_offset + i, step_counter + t, or the injected plane u); action = #{j : cs_j < u} clamped to
+ * n_act - 1, cs the float32 running sum of the state's table row in index order (rllab/misc/special.py:10-19); the
+ * transition of get_possible_next_states / step (0 left, 1 down, 2 right, 3 up; clipped at the border; a wall leaves the
+ * state where it is; a hole: reward 0, done; the goal: reward 1, done); ts += 1, done |= ts >= max_path_length
+ * (max_path_length 0: no horizon); a done env restarts at start_state with ts = 0 and the next recorded observation is
+ * the reset one.  reset_at_start == 0 continues from state / ts.  The launch consumes counters step_counter ..
+ * step_counter + horizon - 1.  n_act must be 4, n_row * n_col at most 1024.  All pointers are device pointers. */
+typedef struct rl_gridworld_args {
+    int32_t n_envs, horizon, max_path_length, reset_at_start;
+    int32_t n_row, n_col, n_act, start_state;
+    int32_t env_offset, reserved;
+    uint64_t seed, step_counter;
+    const int8_t* cell;      /* [n_row * n_col]: 0 free or start, 1 wall, 2 hole, 3 goal */
+    const float* prob;       /* [n_act][n_states] */
+    const float* u;          /* optional [horizon][n_envs] uniforms in [0, 1) */
+    int32_t* state;          /* [n_envs] in / out */
+    int32_t* ts;             /* [n_envs] in / out */
+    float* obs;              /* [n_states][horizon][n_envs] one-hot */
+    float* actions;          /* [n_act][horizon][n_envs] one-hot */
+    float* prob_out;         /* [n_act][horizon][n_envs] the table column of the recorded state */
+    float* rewards;          /* [horizon][n_envs] */
+    uint8_t* dones;          /* [horizon][n_envs] */
+} rl_gridworld_args;
+int rl_rollout_gridworld(const rl_gridworld_args* args, void* stream);
+
+/* prob[n_act][B] = softmax over the action axis of logits[n_act][B], max-subtracted; n_act <= 8. */
+int rl_categorical_softmax(size_t n_samples, int n_act, const float* logits, float* prob, void* stream);
+
+/* The categorical head on planes [n_act][B] (rllab/distributions/categorical.py:32-73 with TINY = 1e-8 where the
+ * reference has it, rllab/algos/npo.py:72-82, rllab/algos/vpg.py:91): out4 as rl_policy_loss_kl with
+ * lr = (p_new.a + TINY) / (p_old.a + TINY), KL = sum_k p_old (log(p_old + TINY) - log(p_new + TINY)),
+ * logp = log(p_new.a + TINY), p_new = softmax(logits), a = the one-hot actions; when g_logits is given, the cotangent
+ * of (-sum_b w {lr | logp} adv + kl_penalty sum_b w KL) * inv_count on the logits (vpg != 0: logp instead of lr).
+ * Per-workgroup partial rows folded in a fixed order by a second launch.  workspace:
+ * rl_categorical_head_workspace_bytes(). */
+size_t rl_categorical_head_workspace_bytes(void);
+int rl_categorical_head(size_t n_samples, int n_act, const float* logits, const float* actions, const float* advantages,
+                        const float* old_prob, const float* weights, float inv_count, int vpg, float kl_penalty,
+                        float* g_logits, void* workspace, size_t workspace_bytes, double* out4, void* stream);
+
+/* g_logits = w inv_count H dlogits per sample, H the Hessian of the per-sample KL above in the new logits at
+ * new == old = softmax(logits) (diag(p) - p p^T at TINY = 0; the reference's TINY is kept). */
+int rl_categorical_fisher(size_t n_samples, int n_act, const float* dlogits, const float* logits, const float* weights,
+                          float inv_count, float* g_logits, void* stream);
+
 /* Vector algebra of krylov.cg (rllab/misc/krylov.py:7-39) for the TRPO descent direction
  * (conjugate_gradient_optimizer.py:253-256), one launch per iteration, float64 like the reference.
  *   rl_cg_init : x = 0, r = p = b, p32 = (float)p, scal = {r.r, active = 1, 0, 0}

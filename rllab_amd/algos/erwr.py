@@ -19,3 +19,10 @@ class ERWR(VPG, Serializable):
             optimizer = LbfgsOptimizer(**(optimizer_args or {}))
         super(ERWR, self).__init__(optimizer=optimizer, positive_adv=True if positive_adv is None else positive_adv,
                                    **kwargs)
+
+    def init_opt(self):
+        from rllab_amd.algos.npo import is_categorical
+        if is_categorical(self.policy):
+            raise NotImplementedError("ERWR on a categorical policy: its L-BFGS fit runs on the Gaussian log-likelihood "
+                                      "kernels only")
+        return super(ERWR, self).init_opt()

@@ -30,6 +30,10 @@ def npo_inputs(policy, samples_data):
         cnt = torch.tensor(float(traj.count), dtype=torch.float64)
     else:
         cnt = D.all_reduce_sum_(w.to(torch.float64).sum())
+    if getattr(traj, "categorical", False):
+        # a categorical policy: (obs, actions, advantages, old_prob, weights, 1/W) -- one-hot planes, recorded probabilities
+        return (traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B), traj.advantages.reshape(B),
+                traj.means.reshape(traj.act_dim, B), w, (1.0 / cnt))
     old_ls = traj.log_std.reshape(-1, 1) if traj.log_std_planes is None \
         else traj.log_std_planes.reshape(traj.act_dim, B)
     return (traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B),
@@ -45,6 +49,20 @@ def log_update_path(policy, fused, why=None):
     if why is None and hasattr(policy, "why_no_kernel_layout"):
         why = policy.why_no_kernel_layout()
     logger.log("update path: torch autograd%s" % ("" if why is None else " -- " + why))
+
+
+def is_categorical(policy):
+    """A policy over discrete actions (CategoricalMLPPolicy): its distribution's parameters are the probabilities."""
+    return list(getattr(policy.distribution, "dist_info_keys", [])) == ["prob"]
+
+
+def check_categorical_supported(policy):
+    """What the categorical path does not do, said in a sentence (called by the algorithms' ``init_opt``)."""
+    if getattr(policy, "num_seq_inputs", 1) != 1:
+        raise NotImplementedError("CategoricalMLPPolicy(num_seq_inputs > 1): the batch planes hold one observation per "
+                                  "sample")
+    if D.is_distributed():
+        raise NotImplementedError("a categorical policy is trained in one process on one GPU (not sharded over ranks)")
 
 
 def pick_optimizer(optimizer, optimizer_args, default_cls, **default_args):
@@ -89,6 +107,19 @@ class NPO(BatchPolopt):
             old = dict(mean=old_mean, log_std=old_log_std)
             kl = dist.kl_sym(old, new, axis=0)
             return (kl * w).sum() * inv_count.to(kl.dtype)
+
+        if is_categorical(policy):
+            check_categorical_supported(policy)
+
+            def surr_loss(flat, obs, act, adv, old_prob, w, inv_count):  # noqa: F811
+                lr = dist.likelihood_ratio_sym(act, dict(prob=old_prob), _new_dist(flat, obs), axis=0)
+                if trunc is not None:
+                    lr = torch.clamp(lr, max=trunc)
+                return -(lr * adv * w).sum() * inv_count.to(lr.dtype)
+
+            def mean_kl(flat, obs, act, adv, old_prob, w, inv_count):  # noqa: F811
+                kl = dist.kl_sym(dict(prob=old_prob), _new_dist(flat, obs), axis=0)
+                return (kl * w).sum() * inv_count.to(kl.dtype)
 
         fused = None
         if trunc is None and hasattr(policy, "fused_ops") and getattr(self, "use_fused", True):

@@ -177,6 +177,9 @@ class REPS(BatchPolopt, Serializable):
             raise NotImplementedError("recurrent policies are outside the hot path built here")
         if D.is_distributed():
             raise NotImplementedError("REPS on env shards: the dual's log-sum-exp is not folded across ranks")
+        if list(getattr(self.policy.distribution, "dist_info_keys", [])) == ["prob"]:
+            raise NotImplementedError("REPS on a categorical policy: its weighted maximum-likelihood fit runs on the "
+                                      "Gaussian log-likelihood kernels only")
         policy = self.policy
         dist = policy.distribution
         # Init dual param values (reps.py:55-57)

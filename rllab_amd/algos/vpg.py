@@ -8,7 +8,7 @@ import torch
 
 import rllab_amd.misc.logger as logger
 from rllab_amd.algos.batch_polopt import BatchPolopt
-from rllab_amd.algos.npo import log_update_path, npo_inputs
+from rllab_amd.algos.npo import check_categorical_supported, is_categorical, log_update_path, npo_inputs
 from rllab_amd.core.serializable import Serializable
 from rllab_amd.optimizers.first_order_optimizer import FirstOrderOptimizer
 from rllab_amd.sampler import dist as D
@@ -45,6 +45,21 @@ class VPG(BatchPolopt, Serializable):
                 neg = torch.full_like(kl, -float("inf"))
                 max_kl = D.all_reduce_max_(torch.where(w > 0, kl, neg).max().to(torch.float64))
             return float(mean_kl), float(max_kl)
+
+        if is_categorical(policy):
+            check_categorical_supported(policy)
+
+            def surr_obj(flat, obs, act, adv, old_prob, w, inv_count):  # noqa: F811
+                logli = dist.log_likelihood_sym(act, policy.dist_info_planes(obs, flat), axis=0)
+                return -(logli * adv * w).sum() * inv_count.to(logli.dtype)
+
+            def f_kl(inputs):  # noqa: F811
+                obs, act, adv, old_prob, w, inv_count = inputs
+                with torch.no_grad():
+                    kl = dist.kl_sym(dict(prob=old_prob), policy.dist_info_planes(obs), axis=0)
+                    mean_kl = ((kl * w).sum() * inv_count.to(kl.dtype)).to(torch.float64)
+                    max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
+                return float(mean_kl), float(max_kl)
 
         fused = policy.fused_ops() if hasattr(policy, "fused_ops") and getattr(self, "use_fused", True) else None
         log_update_path(policy, fused)

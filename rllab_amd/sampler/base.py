@@ -68,6 +68,8 @@ class SamplesData(dict):
             val = vec(tr.returns)
         elif key == "advantages":
             val = vec(tr.advantages)
+        elif key == "agent_infos" and getattr(tr, "categorical", False):
+            val = dict(prob=rows(tr.means))
         elif key == "agent_infos":
             mean = rows(tr.means)
             val = dict(mean=mean, log_std=rows(tr.log_std_planes) if tr.log_std_planes is not None
@@ -109,7 +111,10 @@ def path_scan(traj, whole_paths, coeffs=None, want_values=True):
         else:   # through pinned memory: a pageable upload would hold the host until the rollout ahead of it is done
             cf = upload_async(np.asarray(coeffs, dtype=np.float64), torch.float64, dev)
         assert cf.numel() == 2 * traj.obs_dim + 4
-    _lib.check(_lib.lib.rl_path_scan(T, N, traj.obs_dim, _lib.ptr(traj.dones), _lib.ptr(traj.obs), _lib.ptr(cf),
+    # (without coefficients the scan reads no observation: a one-hot batch wider than the feature kernels' 21 rows --
+    # GridWorld '8x8' -- is scanned like the sampler's own path index)
+    obs_dim = traj.obs_dim if (cf is not None or traj.obs_dim <= 21) else 0
+    _lib.check(_lib.lib.rl_path_scan(T, N, obs_dim, _lib.ptr(traj.dones), _lib.ptr(traj.obs) if obs_dim else None, _lib.ptr(cf),
                                      int(bool(whole_paths)), _lib.ptr(tin), _lib.ptr(valid), _lib.ptr(values),
                                      _lib.stream_ptr()), "rl_path_scan")
     return tin, valid.view(torch.bool), values     # 0 / 1 bytes: the same storage seen as bool
@@ -184,6 +189,14 @@ def process_dense(algo, itr, traj, log=True):
     # the iteration's one blocking host read: batch statistics and, riding along, the recorded log_std row
     # (Entropy, AveragePolicyStd)
     dense_fit = hasattr(baseline, "fit_dense")
+    pdist = algo.policy.distribution
+    # a categorical policy (discrete actions): the batch carries the recorded "prob" planes and nothing Gaussian
+    categorical = getattr(traj, "categorical", False)
+    if categorical and D.is_distributed():
+        raise NotImplementedError("a categorical batch is processed in one process on one GPU (not sharded over ranks)")
+    if categorical and type(baseline).__name__ == "GaussianMLPBaseline":
+        raise NotImplementedError("GaussianMLPBaseline on a categorical batch: its fused regressor is built for the "
+                                  "continuous envs' observations; use LinearFeatureBaseline or ZeroBaseline")
     if dense_fit and log:
         logger.log("fitting baseline...")
     if dense_fit and D.is_distributed() and hasattr(baseline, "normal_eq_dense"):
@@ -194,6 +207,11 @@ def process_dense(algo, itr, traj, log=True):
         stats_read = read_async(rows[:, :st.numel()].contiguous())
         baseline.fit_from_packed(rows[:, st.numel():].sum(dim=0), 2 * traj.obs_dim + 4)
         dense_fit_done = True
+    elif categorical:
+        # the entropy sum rides behind the statistics row: still ONE blocking host read per iteration
+        ent_sum = (pdist.entropy_sym(dict(prob=traj.means.to(torch.float64)), axis=0) * valid.to(torch.float64)).sum()
+        stats_read = read_async(torch.cat([st, ent_sum.reshape(1)]).reshape(1, -1))
+        dense_fit_done = False
     else:
         stats_read = read_async(D.all_gather_rows(st))      # [world, 20]: one collective, folded on the host
         dense_fit_done = False
@@ -202,7 +220,11 @@ def process_dense(algo, itr, traj, log=True):
     # validity are on the device already): queue them behind the statistics so the device works through the wait
     if dense_fit and not dense_fit_done:
         baseline.fit_dense(traj, all_reduce=D.all_reduce_sum_ if D.is_distributed() else None)
-    s = fold_stats(stats_read.get())
+    if categorical:
+        host = stats_read.get().reshape(-1)
+        s, ent_sum_host = fold_stats(host[:20]), float(host[20])
+    else:
+        s = fold_stats(stats_read.get())
     traj.log_std_host = ls_read.get().astype(np.float64) if ls_read is not None else None
     cnt, n_paths = s[_COUNT], s[_NPATH]
     traj.count = float(cnt)                   # global number of valid samples (npo_inputs: 1 / W)
@@ -246,8 +268,9 @@ def process_dense(algo, itr, traj, log=True):
     _SHIFT["ret"], _SHIFT["und"] = float(m_ret + _SHIFT["ret"]), (float(mean_und) if n_paths > 0 else 0.0)
 
     # Entropy = mean over samples of the policy entropy (reference :93)
-    pdist = algo.policy.distribution
-    if traj.log_std_planes is not None and hasattr(pdist, "entropy_sym"):
+    if categorical:
+        ent = ent_sum_host / cnt
+    elif traj.log_std_planes is not None and hasattr(pdist, "entropy_sym"):
         e = pdist.entropy_sym(dict(log_std=traj.log_std_planes.to(torch.float64)), axis=0)
         (es,) = D.sums((e * valid.to(torch.float64)).sum())
         ent = float(es) / cnt

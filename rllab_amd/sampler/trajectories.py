@@ -9,6 +9,9 @@ b = t*N + n):
     log_std  [Da]         agent_info "log_std" is one constant row (state-independent)
     rewards  [T, N]
     dones    [T, N] uint8 env done OR ts == max_path_length
+A batch of a categorical policy (``categorical=True``: discrete actions, ``dist_info_keys == ["prob"]``) holds one-hot
+``obs`` / ``actions`` planes, the recorded action probabilities (agent_info "prob") where the Gaussian batch holds the
+means, and no log_std.
 A *path* is a maximal run of consecutive t in one env column that ends at a
 done flag or at the last recorded step.  Nothing here copies B-sized data to the
 host: per-path Python dicts are materialised lazily, one path at a time, only if
@@ -19,8 +22,10 @@ import torch
 
 
 class Trajectories(object):
-    def __init__(self, obs, actions, means, log_std, rewards, dones, max_path_length, log_std_planes=None):
+    def __init__(self, obs, actions, means, log_std, rewards, dones, max_path_length, log_std_planes=None,
+                 categorical=False):
         self.obs, self.actions, self.means = obs, actions, means
+        self.categorical = bool(categorical)     # ``means`` are the recorded "prob" planes [A, T, N]; log_std is None
         self.log_std, self.rewards, self.dones = log_std, rewards, dones
         # [Da, T, N] per-sample log_std, only for batches packed from arbitrary user paths whose
         # policy does not have a state-independent log_std (None for engine rollouts)
@@ -57,7 +62,7 @@ class Trajectories(object):
         cat = lambda name, dim: (None if getattr(first, name) is None
                                  else torch.cat([getattr(c, name) for c in chunks], dim=dim))
         return cls(cat("obs", 1), cat("actions", 1), cat("means", 1), first.log_std, cat("rewards", 0), cat("dones", 0),
-                   first.max_path_length, log_std_planes=cat("log_std_planes", 1))
+                   first.max_path_length, log_std_planes=cat("log_std_planes", 1), categorical=first.categorical)
 
     def first_steps(self, steps):
         """The batch cut after ``steps`` lock steps (contiguous copies; ``self`` when nothing is cut)."""
@@ -66,7 +71,7 @@ class Trajectories(object):
         cut3 = lambda x: None if x is None else x[:, :steps, :].contiguous()
         return Trajectories(cut3(self.obs), cut3(self.actions), cut3(self.means), self.log_std,
                             self.rewards[:steps].contiguous(), self.dones[:steps].contiguous(), self.max_path_length,
-                            log_std_planes=cut3(self.log_std_planes))
+                            log_std_planes=cut3(self.log_std_planes), categorical=self.categorical)
 
     @property
     def B(self):
@@ -162,9 +167,10 @@ class PathList(object):
             observations=f64(tr.obs[:, a:b, n].t()),
             actions=f64(tr.actions[:, a:b, n].t()),
             rewards=f64(tr.rewards[a:b, n]),
-            agent_infos=dict(mean=f64(tr.means[:, a:b, n].t()),
-                             log_std=(f64(tr.log_std_planes[:, a:b, n].t()) if tr.log_std_planes is not None
-                                      else np.tile(f64(tr.log_std)[None, :], (L, 1)))),
+            agent_infos=dict(prob=f64(tr.means[:, a:b, n].t())) if tr.categorical else
+            dict(mean=f64(tr.means[:, a:b, n].t()),
+                 log_std=(f64(tr.log_std_planes[:, a:b, n].t()) if tr.log_std_planes is not None
+                          else np.tile(f64(tr.log_std)[None, :], (L, 1)))),
             env_infos=dict(),
         )
         if tr.advantages is not None:
