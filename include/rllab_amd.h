@@ -677,6 +677,23 @@ int rl_categorical_head(size_t n_samples, int n_act, const float* logits, const 
 int rl_categorical_fisher(size_t n_samples, int n_act, const float* dlogits, const float* logits, const float* weights,
                           float inv_count, float* g_logits, void* stream);
 
+/* The covariance update of CMA-ES (rllab/algos/cma_es_lib.py:3800-3814, the full-matrix case with CMA_active), both
+ * N x N float64 matrices in ONE pass, in place:
+ *   Yneg[i][j] <- scal[2] Yneg[i][j] + sum_k wneg[k] Vneg[k][i] Vneg[k][j] - C_old[i][j]       (scal[2] = 1 - cmuexp)
+ *   C[i][j]    <- scal[0] C_old[i][j] + sum_k wpos[k] Ypos[k][i] Ypos[k][j] + scal[1] pc[i] pc[j]
+ *                                                                  (scal[0] = 1 - c1a - cmu, scal[1] = c1)
+ *   dC[i]      <- C[i][i]
+ * C, Yneg: double, row stride ld >= N elements (entries outside the N x N corner are not touched);  Ypos double[mu][N]
+ * (the best mu steps, (x - mean_old) / sigma), wpos double[mu] (cmu * weights);  Vneg double[mu_neg][N] (the worst steps,
+ * rescaled to Mahalanobis length sqrt(N)), wneg double[mu_neg];  pc, dC double[N];  scal: three doubles in DEVICE memory
+ * (c1a depends on hsig of the same iteration: nothing is read back before the launch).  Yneg NULL (then Vneg / wneg are
+ * not read): CMA_active off, only C and dC are updated.  Any N, mu >= 1, mu_neg >= 0.  Fixed summation order (k ascending,
+ * then the rank-one term), every term fma(w, round(a_i a_j), acc): with symmetric C and Yneg the results are exactly
+ * symmetric, and equal inputs give equal bits.  All device pointers. */
+int rl_cmaes_cov_update(int N, int ld, int mu, int mu_neg, double* C, double* Yneg, double* dC, const double* Ypos,
+                        const double* wpos, const double* Vneg, const double* wneg, const double* pc, const double* scal,
+                        void* stream);
+
 /* Vector algebra of krylov.cg (rllab/misc/krylov.py:7-39) for the TRPO descent direction
  * (conjugate_gradient_optimizer.py:253-256), one launch per iteration, float64 like the reference.
  *   rl_cg_init : x = 0, r = p = b, p32 = (float)p, scal = {r.r, active = 1, 0, 0}

@@ -35,7 +35,7 @@ SYMBOLS = [
     "rl_peer_allreduce_sum",
     "rl_mlp_forward", "rl_mlp_forward_ws", "rl_mlp_backward", "rl_gaussian_head_workspace_bytes", "rl_gaussian_head", "rl_gaussian_fisher",
     "rl_rollout_gridworld", "rl_categorical_softmax", "rl_categorical_head_workspace_bytes", "rl_categorical_head",
-    "rl_categorical_fisher",
+    "rl_categorical_fisher", "rl_cmaes_cov_update",
 ]
 
 
@@ -272,6 +272,7 @@ def _load():
     lib.rl_categorical_head_workspace_bytes.argtypes = []
     lib.rl_categorical_head.argtypes = [sz, i32, vp, vp, vp, vp, vp, f32, i32, f32, vp, vp, sz, vp, vp]
     lib.rl_categorical_fisher.argtypes = [sz, i32, vp, vp, vp, f32, vp, vp]
+    lib.rl_cmaes_cov_update.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     vpp = ctypes.POINTER(ctypes.c_void_p)
     lib.rl_peer_mailbox_bytes.restype = sz
     lib.rl_peer_mailbox_bytes.argtypes = [i32, i32]

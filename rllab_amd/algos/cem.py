@@ -59,6 +59,42 @@ def cem_sample_prefix(lengths, batch_size):
     return int(reached[0]) + 1 if reached.numel() else None
 
 
+def population_why_unsupported(env, policy, plot=False):
+    """One sentence naming what keeps this env / policy / plot setting off the population rollout, or None (shared by the
+    algorithms that evaluate candidates there: CEM, CMAES)."""
+    from rllab_amd.envs.hip_env import HipEnv
+    from rllab_amd.envs.normalized_env import NormalizedEnv
+    from rllab_amd.policies.gaussian_mlp_policy import GaussianMLPPolicy, is_rectify
+    from rllab_amd.policies.kernel_layout import tile_for
+    from rllab_amd.sampler import dist as D
+    if plot:
+        return "plot=True: plotting is out of scope of the engine"
+    if D.is_distributed():
+        return "a distributed run: the population rollout evaluates its candidates on one device"
+    if isinstance(env, NormalizedEnv):
+        if env._normalize_obs or env._normalize_reward:
+            return ("normalize(env, normalize_obs / normalize_reward): the running estimates of a NormalizedEnv are not "
+                    "part of the population rollout")
+        env = env._wrapped_env
+    if not isinstance(env, HipEnv):
+        return "%s is not a HIP-native env (optionally wrapped in normalize)" % type(env).__name__
+    if env._position_ids is not None:
+        return "position_only observations: the candidates' first layers are built on the kept rows"
+    if not isinstance(policy, GaussianMLPPolicy):
+        return "%s is not a GaussianMLPPolicy" % type(policy).__name__
+    if policy.state_dependent_std:
+        return "the log-std is a network (adaptive_std / std_network): the population kernel takes one log_std row per candidate"
+    if is_rectify(policy.hidden_nonlinearity):
+        return "hidden_nonlinearity is rectify: the population kernel evaluates tanh layers"
+    hs = tuple(int(h) for h in policy.hidden_sizes)
+    if not ((len(hs) == 1 and 1 <= hs[0] <= 64) or tile_for(hs) is not None):
+        return ("hidden_sizes=%r: the population kernel runs two hidden layers of at most 64 units each, or one of at "
+                "most 64" % (hs,))
+    if policy.kernel_layout() is None:
+        return policy.why_no_kernel_layout()
+    return None
+
+
 class CEM(RLAlgorithm, Serializable):
     def __init__(
             self,
@@ -118,39 +154,7 @@ class CEM(RLAlgorithm, Serializable):
 
     def why_unsupported(self):
         """One sentence naming what keeps this configuration off the population rollout, or None."""
-        from rllab_amd.envs.hip_env import HipEnv
-        from rllab_amd.envs.normalized_env import NormalizedEnv
-        from rllab_amd.policies.gaussian_mlp_policy import GaussianMLPPolicy, is_rectify
-        from rllab_amd.policies.kernel_layout import tile_for
-        from rllab_amd.sampler import dist as D
-        if self.plot:
-            return "plot=True: plotting is out of scope of the engine"
-        if D.is_distributed():
-            return "a distributed run: the population rollout evaluates its candidates on one device"
-        env = self.env
-        if isinstance(env, NormalizedEnv):
-            if env._normalize_obs or env._normalize_reward:
-                return ("normalize(env, normalize_obs / normalize_reward): the running estimates of a NormalizedEnv are not "
-                        "part of the population rollout")
-            env = env._wrapped_env
-        if not isinstance(env, HipEnv):
-            return "%s is not a HIP-native env (optionally wrapped in normalize)" % type(env).__name__
-        if env._position_ids is not None:
-            return "position_only observations: the candidates' first layers are built on the kept rows"
-        policy = self.policy
-        if not isinstance(policy, GaussianMLPPolicy):
-            return "%s is not a GaussianMLPPolicy" % type(policy).__name__
-        if policy.state_dependent_std:
-            return "the log-std is a network (adaptive_std / std_network): the population kernel takes one log_std row per candidate"
-        if is_rectify(policy.hidden_nonlinearity):
-            return "hidden_nonlinearity is rectify: the population kernel evaluates tanh layers"
-        hs = tuple(int(h) for h in policy.hidden_sizes)
-        if not ((len(hs) == 1 and 1 <= hs[0] <= 64) or tile_for(hs) is not None):
-            return ("hidden_sizes=%r: the population kernel runs two hidden layers of at most 64 units each, or one of at "
-                    "most 64" % (hs,))
-        if policy.kernel_layout() is None:
-            return policy.why_no_kernel_layout()
-        return None
+        return population_why_unsupported(self.env, self.policy, self.plot)
 
     def train(self):
         reason = self.why_unsupported()
