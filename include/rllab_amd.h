@@ -376,6 +376,55 @@ typedef struct rl_population_args {
 
 int rl_rollout_population(const rl_population_args* args, void* stream);
 
+/* Recurrent rollout: the fused rollout of a GaussianGRUPolicy (rllab/policies/gaussian_gru_policy.py:17-159,
+ * rllab/core/network.py:104-155).  Env-per-lane like the population rollout (rollout_gru_kernel<Env, H>,
+ * csrc/gru_kernels.hip): every env is stepped `horizon` times with auto-reset exactly as rl_rollout_gaussian_mlp steps it
+ * (same Philox streams keyed by (seed, env_offset + i, step_counter + t); the launch consumes horizon + 1 counters), its
+ * action mean coming from one GRU step per env step on x = [obs, prev_action] (obs alone with include_action = 0):
+ *   r = sigmoid(x W_xr + h W_hr + b_r)     u = sigmoid(x W_xu + h W_hu + b_u)
+ *   c = tanh(x W_xc + r * (h W_hc) + b_c)  h' = (1 - u) h + u c     mean = h' W_out + b_out
+ * in float32 FMAs in input-index order.  prev_action is the SAMPLED action mean + eps * exp(log_std) of the previous step
+ * of the same path, zeros at a path start; h is h0 at a path start (env done, or forced at max_path_length).
+ * theta: h0[H], W_xr[DI][H], W_hr[H][H], b_r[H], W_xu, W_hu, b_u, W_xc, W_hc, b_c, W_out[H][act_dim], b_out[act_dim],
+ * log_std[act_dim] with DI = obs_dim + (include_action ? act_dim : 0) and every W stored [in][out] row-major.
+ * hidden_state / prev_action are carried between launches: written at the end of every launch, read at the start of one
+ * with reset_at_start = 0 (which also carries on from state, ts and last_obs).
+ * hidden must be 32 or 64 (narrower layers: zero padding, exact); anything else is RL_ERR_UNSUPPORTED, as are the
+ * soft-constraint steps RL_CFG_LIMIT_MUJOCO / RL_CFG_CONTACT_MUJOCO of the legged envs. */
+typedef struct rl_gru_rollout_args {
+    int32_t kind;             /* rl_env_kind */
+    int32_t n_envs;
+    int32_t horizon;          /* T: steps per env in this call */
+    int32_t max_path_length;  /* forced done when ts reaches it */
+    int32_t normalize;        /* NormalizedEnv action map on/off */
+    int32_t reset_at_start;   /* 1: reset every env (and h, prev_action) first; 0: carry on from the buffers below */
+    int32_t hidden;           /* 32 or 64 */
+    int32_t include_action;   /* state_include_action: x = [obs, prev_action] */
+    int32_t env_offset;       /* global index of env 0 (RNG key) */
+    float scale_reward;
+    uint64_t seed;
+    uint64_t step_counter;    /* global step index of t = 0 (RNG counter base) */
+    float* state;             /* float[state_dim][n]  in/out */
+    int32_t* ts;              /* int32[n]             in/out */
+    float* last_obs;          /* float[obs_dim][n]    in/out: the observation the next launch starts from */
+    float* hidden_state;      /* float[hidden][n]     in/out */
+    float* prev_action;       /* float[act_dim][n]    in/out */
+    const float* theta;       /* device, the layout above */
+    const float* eps;         /* NULL or float[act_dim][T][n] injected N(0,1) policy noise */
+    const float* reset_draws; /* NULL or float[T+1][reset_draws][n]: slice 0 = initial reset, slice t+1 = reset after step t */
+    const float* act_noise_z; /* NULL or float[T][act_dim][n] injected draws of the env's action noise */
+    const float* obs_noise_z; /* NULL or float[T+1][obs_dim][n] injected draws of the env's observation noise */
+    float* obs;               /* float[obs_dim][T][n] */
+    float* actions;           /* float[act_dim][T][n] */
+    float* means;             /* float[act_dim][T][n] */
+    float* rewards;           /* float[T][n] */
+    uint8_t* dones;           /* uint8[T][n] */
+    const rl_env_cfg* cfg;    /* host; NULL = the env's defaults (its action_noise_z / obs_noise_z are not read here) */
+    const rl_launch_opts* opts;   /* host; NULL.  Reserved: the launch has one shape, 64 envs per single-wavefront workgroup */
+} rl_gru_rollout_args;
+
+int rl_rollout_gaussian_gru(const rl_gru_rollout_args* args, void* stream);
+
 /* Segmented reverse linear-recurrence scans over [T][n] planes, fused:
  *   delta[t] = r[t] + gamma * V[t+1] * (1 - end[t]) - V[t]
  *   adv[t]   = delta[t] + gamma*lambda * (1 - end[t]) * adv[t+1]

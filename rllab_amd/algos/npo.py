@@ -34,6 +34,13 @@ def npo_inputs(policy, samples_data):
         # a categorical policy: (obs, actions, advantages, old_prob, weights, 1/W) -- one-hot planes, recorded probabilities
         return (traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B), traj.advantages.reshape(B),
                 traj.means.reshape(traj.act_dim, B), w, (1.0 / cnt))
+    if getattr(policy, "recurrent", False):
+        # a recurrent policy: the planes stay [., T, N] -- its forward pass is a scan over t of every env column -- and the
+        # path starts ride along: (obs, actions, advantages, old mean, old log_std, start, weights, 1/W)
+        if traj.log_std_planes is not None:
+            raise NotImplementedError("a recurrent batch with per-sample log_std planes")
+        return (traj.obs, traj.actions, traj.advantages, traj.means, traj.log_std.reshape(-1, 1, 1),
+                (traj.tin == 0), traj.valid.to(torch.float32), (1.0 / cnt))
     old_ls = traj.log_std.reshape(-1, 1) if traj.log_std_planes is None \
         else traj.log_std_planes.reshape(traj.act_dim, B)
     return (traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B),
@@ -65,6 +72,15 @@ def check_categorical_supported(policy):
         raise NotImplementedError("a categorical policy is trained in one process on one GPU (not sharded over ranks)")
 
 
+def check_recurrent_supported(policy, optimizer=None):
+    """What the recurrent path does not do, said in a sentence (called by the algorithms' ``init_opt``)."""
+    if D.is_distributed():
+        raise NotImplementedError("a recurrent policy is trained in one process on one GPU (not sharded over ranks)")
+    if getattr(optimizer, "_subsample_factor", 1.0) < 1:
+        raise NotImplementedError("ConjugateGradientOptimizer(subsample_factor < 1) with a recurrent policy: a subsample "
+                                  "must keep whole paths, the optimizer draws single samples")
+
+
 def pick_optimizer(optimizer, optimizer_args, default_cls, **default_args):
     """The optimizer an NPO variant runs with: the one handed in, else ``default_cls`` built from the
     variant's defaults overridden by ``optimizer_args``."""
@@ -85,8 +101,6 @@ class NPO(BatchPolopt):
         super(NPO, self).__init__(**kwargs)
 
     def init_opt(self):
-        if self.policy.recurrent:
-            raise NotImplementedError("recurrent policies are outside the hot path built here")
         policy = self.policy
         dist = policy.distribution
         trunc = self.truncate_local_is_ratio
@@ -108,6 +122,22 @@ class NPO(BatchPolopt):
             kl = dist.kl_sym(old, new, axis=0)
             return (kl * w).sum() * inv_count.to(kl.dtype)
 
+        if policy.recurrent:
+            check_recurrent_supported(policy, self.optimizer)
+
+            # the reference's masked means over [paths, max_path_length] (npo.py:72-79 with ``valids``) on the dense planes
+            def surr_loss(flat, obs, act, adv, old_mean, old_log_std, start, w, inv_count):  # noqa: F811
+                new = policy.dist_info_planes(obs, act, start, flat)
+                lr = dist.likelihood_ratio_sym(act, dict(mean=old_mean, log_std=old_log_std), new, axis=0)
+                if trunc is not None:
+                    lr = torch.clamp(lr, max=trunc)
+                return -(lr * adv * w).sum() * inv_count.to(lr.dtype)
+
+            def mean_kl(flat, obs, act, adv, old_mean, old_log_std, start, w, inv_count):  # noqa: F811
+                new = policy.dist_info_planes(obs, act, start, flat)
+                kl = dist.kl_sym(dict(mean=old_mean, log_std=old_log_std), new, axis=0)
+                return (kl * w).sum() * inv_count.to(kl.dtype)
+
         if is_categorical(policy):
             check_categorical_supported(policy)
 
@@ -122,10 +152,13 @@ class NPO(BatchPolopt):
                 return (kl * w).sum() * inv_count.to(kl.dtype)
 
         fused = None
-        if trunc is None and hasattr(policy, "fused_ops") and getattr(self, "use_fused", True):
+        if policy.recurrent:
+            log_update_path(policy, None)
+        elif trunc is None and hasattr(policy, "fused_ops") and getattr(self, "use_fused", True):
             fused = policy.fused_ops()
-        log_update_path(policy, fused, "truncate_local_is_ratio is set (the kernels evaluate the plain likelihood ratio)"
-                        if trunc is not None else None)
+        if not policy.recurrent:
+            log_update_path(policy, fused, "truncate_local_is_ratio is set (the kernels evaluate the plain likelihood "
+                                           "ratio)" if trunc is not None else None)
         self.optimizer.update_opt(loss=surr_loss, target=policy, leq_constraint=(mean_kl, self.step_size),
                                   inputs=None, constraint_name="mean_kl", fused=fused)
         return dict()

@@ -8,7 +8,8 @@ import torch
 
 import rllab_amd.misc.logger as logger
 from rllab_amd.algos.batch_polopt import BatchPolopt
-from rllab_amd.algos.npo import check_categorical_supported, is_categorical, log_update_path, npo_inputs
+from rllab_amd.algos.npo import (check_categorical_supported, check_recurrent_supported, is_categorical, log_update_path,
+                                 npo_inputs)
 from rllab_amd.core.serializable import Serializable
 from rllab_amd.optimizers.first_order_optimizer import FirstOrderOptimizer
 from rllab_amd.sampler import dist as D
@@ -26,8 +27,6 @@ class VPG(BatchPolopt, Serializable):
         super(VPG, self).__init__(env=env, policy=policy, baseline=baseline, **kwargs)
 
     def init_opt(self):
-        if self.policy.recurrent:
-            raise NotImplementedError("recurrent policies are outside the hot path built here")
         policy = self.policy
         dist = policy.distribution
 
@@ -46,6 +45,23 @@ class VPG(BatchPolopt, Serializable):
                 max_kl = D.all_reduce_max_(torch.where(w > 0, kl, neg).max().to(torch.float64))
             return float(mean_kl), float(max_kl)
 
+        if policy.recurrent:
+            check_recurrent_supported(policy, self.optimizer)
+
+            # the reference's masked means (vpg.py:60-75 with ``valids``) on the dense [., T, N] planes
+            def surr_obj(flat, obs, act, adv, old_mean, old_log_std, start, w, inv_count):  # noqa: F811
+                logli = dist.log_likelihood_sym(act, policy.dist_info_planes(obs, act, start, flat), axis=0)
+                return -(logli * adv * w).sum() * inv_count.to(logli.dtype)
+
+            def f_kl(inputs):  # noqa: F811
+                obs, act, adv, old_mean, old_log_std, start, w, inv_count = inputs
+                with torch.no_grad():
+                    kl = dist.kl_sym(dict(mean=old_mean, log_std=old_log_std), policy.dist_info_planes(obs, act, start),
+                                     axis=0)
+                    mean_kl = ((kl * w).sum() * inv_count.to(kl.dtype)).to(torch.float64)
+                    max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
+                return float(mean_kl), float(max_kl)
+
         if is_categorical(policy):
             check_categorical_supported(policy)
 
@@ -61,7 +77,8 @@ class VPG(BatchPolopt, Serializable):
                     max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
                 return float(mean_kl), float(max_kl)
 
-        fused = policy.fused_ops() if hasattr(policy, "fused_ops") and getattr(self, "use_fused", True) else None
+        fused = policy.fused_ops() if hasattr(policy, "fused_ops") and getattr(self, "use_fused", True) \
+            and not policy.recurrent else None
         log_update_path(policy, fused)
         if fused is not None:
             def f_kl(inputs):  # noqa: F811  (HIP kernel version of the same statistic)

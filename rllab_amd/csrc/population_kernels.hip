@@ -121,30 +121,6 @@ __device__ __forceinline__ void population_forward(const float* __restrict__ the
     }
 }
 
-// Env.step with the launch's options: step_one (rollout_lane.h) with the perturbation array ALWAYS handed to Env::step.
-// step_cfg passes "no action noise" as a null pointer, and an array that is either null or live is addressed through
-// memory: the 4 * ACT + 4 bytes of scratch every env-per-lane kernel reports.  Here the array is always live and holds
-// -0.0f when the option is off -- the additive identity of IEEE addition for EVERY x, the zeros of either sign included
-// (x + -0 = x), so `applied = act + dact[k]` is `applied = act` bit for bit, and the clamps behind it see the value
-// they would have seen -- and stays in registers.  With the option on: the draws and perturbation of step_one / step_cfg.
-template <class Env>
-__device__ __forceinline__ void step_lane(float* s, const float* a, int normalize, const EnvCfg& cfg,
-                                          const float* __restrict__ z, int n, int i, uint64_t seed, uint32_t env_global,
-                                          uint64_t step, float* o, float& r, bool& d) {
-    StepOpts<float> opts = opts_from_cfg<float>(cfg);
-    float dact[Env::ACT];
-    if (cfg.action_noise != 0.0f) {
-        float zn[Env::ACT];
-        noise_draws<Env::ACT>(zn, z, n, i, seed, env_global, step, RNG_ACT_NOISE);
-        action_perturbation<Env, float>(cfg, zn, dact);
-    } else {
-#pragma unroll
-        for (int k = 0; k < Env::ACT; ++k) dact[k] = -0.0f;
-    }
-    opts.dact = dact;
-    Env::template step<float>(s, a, normalize, o, r, d, opts);
-}
-
 template <class Env, int H>
 __global__ void __launch_bounds__(POP_BLOCK) rollout_population_kernel(PopulationDev a) {
     __shared__ float h0_tile[H * WV];

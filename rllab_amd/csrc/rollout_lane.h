@@ -1,6 +1,6 @@
 // rollout_lane.h -- the per-lane pieces every env-per-lane kernel is made of: state planes in and out, reset and noise
 // draws (injected planes or the Philox streams), the observed observation, one Env::step under the launch's options, the
-// walking plane store, and the host-side check of an rl_env_cfg.  Shared by env_kernels.hip and population_kernels.hip.
+// walking plane store, and the host-side check of an rl_env_cfg.  Shared by env_kernels.hip, population_kernels.hip and gru_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -79,6 +79,31 @@ __device__ __forceinline__ void step_one(float* s, const float* a, int normalize
     float zn[Env::ACT];
     if (cfg.action_noise != 0.0f) noise_draws<Env::ACT>(zn, z, n, i, seed, env_global, step, RNG_ACT_NOISE);
     step_cfg<Env, float>(s, a, normalize, cfg, zn, o, r, d);
+}
+
+// Env.step with the launch's options for the kernels that keep one env per lane and a per-lane policy next to it
+// (population_kernels.hip, gru_kernels.hip): step_one with the perturbation array ALWAYS handed to Env::step.
+// step_cfg passes "no action noise" as a null pointer, and an array that is either null or live is addressed through
+// memory: the 4 * ACT + 4 bytes of scratch every env-per-lane kernel reports.  Here the array is always live and holds
+// -0.0f when the option is off -- the additive identity of IEEE addition for EVERY x, the zeros of either sign included
+// (x + -0 = x), so `applied = act + dact[k]` is `applied = act` bit for bit, and the clamps behind it see the value
+// they would have seen -- and stays in registers.  With the option on: the draws and perturbation of step_one / step_cfg.
+template <class Env>
+__device__ __forceinline__ void step_lane(float* s, const float* a, int normalize, const EnvCfg& cfg,
+                                          const float* __restrict__ z, int n, int i, uint64_t seed, uint32_t env_global,
+                                          uint64_t step, float* o, float& r, bool& d) {
+    StepOpts<float> opts = opts_from_cfg<float>(cfg);
+    float dact[Env::ACT];
+    if (cfg.action_noise != 0.0f) {
+        float zn[Env::ACT];
+        noise_draws<Env::ACT>(zn, z, n, i, seed, env_global, step, RNG_ACT_NOISE);
+        action_perturbation<Env, float>(cfg, zn, dact);
+    } else {
+#pragma unroll
+        for (int k = 0; k < Env::ACT; ++k) dact[k] = -0.0f;
+    }
+    opts.dact = dact;
+    Env::template step<float>(s, a, normalize, o, r, d, opts);
 }
 
 // v[0..NP) -> NP planes of a [NP][T][n] array at (t, i): the scalar row pointer walks the planes (one s_add_u32 /

@@ -191,7 +191,19 @@ class HipVecEnv(object):
         layout (or its two networks) and the weight fragments of a wide / deep / dual-network shape fit the LDS of a CU
         next to the env's observation tile (rl_rollout_lds_bytes) -- e.g. a (128,128) mean net + a (128,128) log-std
         net on a 20-observation env needs 172 KB and is sampled through the per-transition loop instead."""
+        if getattr(policy, "recurrent", False):
+            return self._takes_recurrent_rollout_of(policy)
         return self.rollout_plan(policy) is not None
+
+    def _takes_recurrent_rollout_of(self, policy):
+        """A GaussianGRUPolicy with a rollout layout is sampled by rl_rollout_gaussian_gru; what that kernel does not
+        do on this executor is said in a sentence."""
+        if not hasattr(policy, "rollout_layout") or policy.rollout_layout() is None:
+            return False
+        if self.position_ids is not None:
+            raise NotImplementedError("Box2DEnv(position_only=True) with a recurrent policy: the recurrent rollout kernel "
+                                      "feeds the GRU the full observation")
+        return True
 
     def rollout_plan(self, policy, horizon=None, norm=None):
         """``_lib.RolloutPlan`` -- kernel, envs per wavefront, wavefronts, workgroup shape, LDS -- of ``rollout(policy, ..)``
@@ -232,6 +244,12 @@ class HipVecEnv(object):
         ``Trajectories``.  ``eps`` [Da, T, n] / ``reset_draws`` [T+1, R, n] / ``action_noise_z`` [T, Da, n] /
         ``obs_noise_z`` [T+1, Do, n] inject pre-generated noise (parity runs).  ``reset_at_start=False``: the envs carry
         on from their state, step count and the observation the previous launch / ``step`` / ``reset`` ended on."""
+        if getattr(policy, "recurrent", False):
+            if norm is not None:
+                raise NotImplementedError("NormalizedEnv(normalize_obs / normalize_reward) with a recurrent policy: the "
+                                          "running estimates are not built into the recurrent rollout kernel")
+            return self._rollout_recurrent(policy, horizon, reset_at_start, eps, reset_draws, action_noise_z, obs_noise_z,
+                                           scale_reward)
         if self.position_ids is not None and norm is not None:
             raise NotImplementedError("position_only observations under running normalisation: the estimates are over "
                                       "the kept rows; sample through the per-transition path")
@@ -309,6 +327,56 @@ class HipVecEnv(object):
             obs = obs.index_select(0, self._pos_index)
         return Trajectories(obs, act, mean, policy.recorded_log_std(), rew, done,
                             self.max_path_length, log_std_planes=log_stds)
+
+    # -- recurrent rollout: a GRU step per env step -------------------------------------
+    def _rollout_recurrent(self, policy, horizon, reset_at_start, eps, reset_draws, action_noise_z, obs_noise_z,
+                           scale_reward):
+        """``rollout`` of a GaussianGRUPolicy (rl_rollout_gaussian_gru): the same planes and injected-noise keywords; the
+        hidden state [H, n] and the previous action [Da, n] are buffers of this executor next to ``state`` / ``ts`` /
+        the last observation, written by every launch and read by one with ``reset_at_start=False``."""
+        if not self._takes_recurrent_rollout_of(policy):
+            why = policy.why_no_rollout_kernel() if hasattr(policy, "why_no_rollout_kernel") else None
+            raise NotImplementedError("no recurrent rollout kernel for this policy: %s" % (
+                why or "%s is not a GaussianGRUPolicy" % type(policy).__name__))
+        T, n = int(horizon), self.n
+        do, da = self.q["obs_dim"], self.q["act_dim"]
+        assert (policy.obs_dim, policy.action_dim) == (do, da), "policy built for another env"
+        H = policy.kernel_hidden
+        theta = policy.rollout_layout()
+        assert theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous()
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if getattr(self, "hidden_state", None) is None or tuple(self.hidden_state.shape) != (H, n):
+            if not reset_at_start:
+                raise ValueError("rollout(reset_at_start=False) of a recurrent policy needs the hidden state a previous "
+                                 "launch of that policy left on this executor")
+            self.hidden_state = torch.zeros((H, n), **f32)
+            self.prev_action = torch.zeros((da, n), **f32)
+        obs = torch.empty((do, T, n), **f32)
+        act = torch.empty((da, T, n), **f32)
+        mean = torch.empty((da, T, n), **f32)
+        rew = torch.empty((T, n), **f32)
+        done = torch.empty((T, n), dtype=torch.uint8, device=self.device)
+        eps = self._plane(eps, (da, T, n))
+        reset_draws = self._plane(reset_draws, (T + 1, self.q["reset_draws"], n))
+        az = self._plane(action_noise_z, (T, da, n))
+        oz = self._plane(obs_noise_z, (T + 1, do, n))
+        self._cfg_with(None, None)
+        args = _lib.GruRolloutArgs(
+            kind=self.kind, n_envs=n, horizon=T, max_path_length=self.max_path_length, normalize=int(self.normalize),
+            reset_at_start=int(bool(reset_at_start)), hidden=H, include_action=int(policy.state_include_action),
+            env_offset=self.env_offset, scale_reward=self.scale_reward if scale_reward is None else float(scale_reward),
+            seed=self.seed, step_counter=self.step_counter,
+            state=self.state.data_ptr(), ts=self.ts.data_ptr(), last_obs=self._obs.data_ptr(),
+            hidden_state=self.hidden_state.data_ptr(), prev_action=self.prev_action.data_ptr(), theta=theta.data_ptr(),
+            eps=None if eps is None else eps.data_ptr(),
+            reset_draws=None if reset_draws is None else reset_draws.data_ptr(),
+            act_noise_z=None if az is None else az.data_ptr(), obs_noise_z=None if oz is None else oz.data_ptr(),
+            obs=obs.data_ptr(), actions=act.data_ptr(), means=mean.data_ptr(), rewards=rew.data_ptr(),
+            dones=done.data_ptr(), cfg=ctypes.pointer(self.cfg), opts=_lib.launch_opts())
+        _lib.check(_lib.lib.rl_rollout_gaussian_gru(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_gaussian_gru")
+        self.step_counter += T + 1            # as rollout(): counter T belongs to the reset after the last step
+        return Trajectories(obs, act, mean, policy.recorded_log_std(), rew, done, self.max_path_length,
+                            prev_action_info=bool(policy.state_include_action))
 
     # -- population rollout: one parameter vector per env ---------------------------
     def rollout_population(self, theta_pop, n_evals, horizon, discount, record=True, eps=None, reset_draws=None,

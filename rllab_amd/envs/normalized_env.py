@@ -183,6 +183,11 @@ class NormalizingVecEnv(object):
     def takes_rollout_of(self, policy):
         """The fused rollout under running normalisation: the generic kernels of the (32,32) / (64,64) policies carry the
         estimates in registers (rl_running_norm); everything else is sampled through reset() / step()."""
+        if getattr(policy, "recurrent", False):
+            which = " / ".join(k for k, on in (("normalize_obs", self.normalize_obs),
+                                               ("normalize_reward", self.normalize_reward)) if on)
+            raise NotImplementedError("NormalizedEnv(%s=True) with a recurrent policy: the running estimates are not "
+                                      "built into the recurrent rollout kernel (plain normalize(env) is)" % which)
         if self.inner.position_ids is not None:
             return False
         return self.inner.rollout_plan(policy, norm=(self.normalize_obs, self.normalize_reward)) is not None

@@ -78,6 +78,9 @@ class FiniteDifferenceHvp(Serializable):
 
     def build_eval(self, inputs, trainable_index=None):
         target, f, reg = self.target, self._f, self.reg_coeff
+        # the dtype the two shifted gradients are evaluated in: the parameters' own, unless the target asks for more
+        # (``fd_hvp_dtype``: a recurrent policy -- see GaussianGRUPolicy)
+        dt = getattr(target, "fd_hvp_dtype", None) or target.flat_params.dtype
 
         def grad_at(theta):
             flat = theta.detach().clone().requires_grad_(True)
@@ -97,13 +100,13 @@ class FiniteDifferenceHvp(Serializable):
                     th = th + sign * eps * x
                 else:
                     th[trainable_index] += sign * eps * x
-                return th.to(target.flat_params.dtype)
+                return th.to(dt)
             gp = grad_at(shifted(+1.0))
             if self.symmetric:
                 gm = grad_at(shifted(-1.0))
                 hx = (gp - gm) / (2 * eps)
             else:
-                hx = (gp - grad_at(theta.to(target.flat_params.dtype))) / eps
+                hx = (gp - grad_at(theta.to(dt))) / eps
             return hx + reg * x
         return eval
 

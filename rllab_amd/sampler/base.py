@@ -1,8 +1,7 @@
 """Sampler interface and sample post-processing.
 
 ``Sampler`` / ``BaseSampler`` keep the surface of rllab/sampler/base.py:10-46.
-``process_samples`` computes what the non-recurrent branch of the reference
-(:48-104, :163-182) computes -- baseline prediction, TD residuals, GAE advantages,
+``process_samples`` computes what the reference (:48-104, :163-182) computes -- baseline prediction, TD residuals, GAE advantages,
 discounted returns, explained variance, advantage centring/shifting, entropy,
 baseline fit and the tabular log -- but on dense device planes:
 
@@ -362,7 +361,5 @@ class BaseSampler(Sampler):
         self.algo = algo
 
     def process_samples(self, itr, paths):
-        if self.algo.policy.recurrent:
-            raise NotImplementedError("recurrent policies are outside the hot path built here")
         traj = paths.traj if isinstance(paths, PathList) else pack_paths(paths)
         return process_dense(self.algo, itr, traj)

@@ -23,9 +23,12 @@ import torch
 
 class Trajectories(object):
     def __init__(self, obs, actions, means, log_std, rewards, dones, max_path_length, log_std_planes=None,
-                 categorical=False):
+                 categorical=False, prev_action_info=False):
         self.obs, self.actions, self.means = obs, actions, means
         self.categorical = bool(categorical)     # ``means`` are the recorded "prob" planes [A, T, N]; log_std is None
+        # a recurrent policy with state_info_keys == ["prev_action"]: paths carry agent_infos["prev_action"], which is
+        # ``actions`` shifted by one step inside a path (zeros at its start) -- nothing extra is stored
+        self.prev_action_info = bool(prev_action_info)
         self.log_std, self.rewards, self.dones = log_std, rewards, dones
         # [Da, T, N] per-sample log_std, only for batches packed from arbitrary user paths whose
         # policy does not have a state-independent log_std (None for engine rollouts)
@@ -62,7 +65,8 @@ class Trajectories(object):
         cat = lambda name, dim: (None if getattr(first, name) is None
                                  else torch.cat([getattr(c, name) for c in chunks], dim=dim))
         return cls(cat("obs", 1), cat("actions", 1), cat("means", 1), first.log_std, cat("rewards", 0), cat("dones", 0),
-                   first.max_path_length, log_std_planes=cat("log_std_planes", 1), categorical=first.categorical)
+                   first.max_path_length, log_std_planes=cat("log_std_planes", 1), categorical=first.categorical,
+                   prev_action_info=first.prev_action_info)
 
     def first_steps(self, steps):
         """The batch cut after ``steps`` lock steps (contiguous copies; ``self`` when nothing is cut)."""
@@ -71,7 +75,8 @@ class Trajectories(object):
         cut3 = lambda x: None if x is None else x[:, :steps, :].contiguous()
         return Trajectories(cut3(self.obs), cut3(self.actions), cut3(self.means), self.log_std,
                             self.rewards[:steps].contiguous(), self.dones[:steps].contiguous(), self.max_path_length,
-                            log_std_planes=cut3(self.log_std_planes), categorical=self.categorical)
+                            log_std_planes=cut3(self.log_std_planes), categorical=self.categorical,
+                            prev_action_info=self.prev_action_info)
 
     @property
     def B(self):
@@ -173,6 +178,9 @@ class PathList(object):
                           else np.tile(f64(tr.log_std)[None, :], (L, 1)))),
             env_infos=dict(),
         )
+        if tr.prev_action_info:
+            acts = path["actions"]
+            path["agent_infos"]["prev_action"] = np.concatenate([np.zeros_like(acts[:1]), acts[:-1]], axis=0)
         if tr.advantages is not None:
             path["advantages"] = f64(tr.advantages[a:b, n])
             path["returns"] = f64(tr.returns[a:b, n])

@@ -66,8 +66,23 @@ class VectorizedSampler(BaseSampler):
             kw["seed"] = self.seed
         self.vec_env = algo.env.vec_env_executor(**kw)
         self.n_envs = n_envs
+        if getattr(algo.policy, "recurrent", False):
+            self._check_recurrent(algo.policy)
         name, why = self.sampling_path(algo.policy)
         logger.log("sampling path: %s%s" % (name, "" if why is None else " -- " + why))
+
+    def _check_recurrent(self, policy):
+        """A recurrent policy is sampled by its fused rollout or not at all: the per-transition loops never call
+        ``policy.reset(dones)``, so they would carry one path's hidden state into the next."""
+        why = policy.why_no_rollout_kernel() if hasattr(policy, "why_no_rollout_kernel") else \
+            "%s has no recurrent rollout kernel" % type(policy).__name__
+        if why is not None:
+            raise NotImplementedError("recurrent policy without a sampling path: %s" % why)
+        if D.is_distributed():
+            raise NotImplementedError("a recurrent policy is sampled and trained in one process on one GPU (not sharded "
+                                      "over ranks)")
+        if not self._takes_fused_rollout(policy):         # (an executor that refuses raises its own sentence)
+            raise NotImplementedError("recurrent policy without a sampling path: this executor has no recurrent rollout")
 
     def sampling_path(self, policy):
         """(name, reason) of the way ``obtain_samples`` will sample ``policy`` on this executor: the fused rollout (one
