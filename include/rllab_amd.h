@@ -706,6 +706,46 @@ typedef struct rl_gridworld_args {
 } rl_gridworld_args;
 int rl_rollout_gridworld(const rl_gridworld_args* args, void* stream);
 
+/* Recurrent GridWorld rollout: the fused rollout of a CategoricalGRUPolicy (rllab/policies/categorical_gru_policy.py:18-188,
+ * rllab/core/network.py:104-155) on the same env (gridworld_gru_rollout_kernel<H>, csrc/categorical_gru_kernels.hip).
+ * A recurrent policy's probabilities depend on each env's hidden state, so there is no table: they are evaluated per env
+ * and per step inside the launch.  One env per lane, one wavefront per workgroup of 64 envs, theta and the hidden state in
+ * LDS.  Per env and step: record the one-hot observation; one GRU step on x = [onehot(s), onehot(prev_action)] (onehot(s)
+ * alone with include_action = 0)
+ *   r = sigmoid(x W_xr + h W_hr + b_r)     u = sigmoid(x W_xu + h W_hu + b_u)
+ *   c = tanh(x W_xc + r * (h W_hc) + b_c)  h' = (1 - u) h + u c     logits = h' W_out + b_out
+ * where x W_x* is a row read: each gate's sum is its bias, row s of W_x*, row S + prev_action of W_x* (skipped at a path
+ * start), then the hidden units in index order in float32 FMAs; prob = the max-subtracted float32 softmax of the logits,
+ * recorded in prob_out; one uniform and the action as rl_rollout_gridworld draws them (same Philox stream and counters,
+ * the launch consumes step_counter .. step_counter + horizon - 1; same cumulative rule); the transition, ts and the
+ * horizon as there.  A done env restarts at start_state with ts = 0, h = h0 and no previous action.
+ * theta: h0[H], W_xr[DI][H], W_hr[H][H], b_r[H], W_xu, W_hu, b_u, W_xc, W_hc, b_c, W_out[H][4], b_out[4] with
+ * DI = n_row * n_col + (include_action ? 4 : 0) and every W stored [in][out] row-major.
+ * state / ts / hidden_state / prev_action are carried between launches: written at the end of every launch, read at the
+ * start of one with reset_at_start = 0.  prev_action is the action INDEX, -1 = none (the path starts here).
+ * n_act must be 4; hidden must be 32 or 64 (narrower layers: zero padding, exact), anything else is RL_ERR_UNSUPPORTED, as
+ * is a map whose weights plus 2 * hidden * 64 floats exceed the 160 KB LDS of a CU (about 340 states at hidden 32, 99 at
+ * hidden 64; the message names the byte count).  All pointers are device pointers. */
+typedef struct rl_gridworld_gru_args {
+    int32_t n_envs, horizon, max_path_length, reset_at_start;
+    int32_t n_row, n_col, n_act, start_state;
+    int32_t env_offset, hidden, include_action, reserved;
+    uint64_t seed, step_counter;
+    const int8_t* cell;      /* [n_row * n_col]: 0 free or start, 1 wall, 2 hole, 3 goal */
+    const float* theta;      /* the layout above */
+    const float* u;          /* optional [horizon][n_envs] uniforms in [0, 1) */
+    int32_t* state;          /* [n_envs] in / out */
+    int32_t* ts;             /* [n_envs] in / out */
+    float* hidden_state;     /* [hidden][n_envs] in / out */
+    int32_t* prev_action;    /* [n_envs] in / out: action index, -1 = no previous action */
+    float* obs;              /* [n_states][horizon][n_envs] one-hot */
+    float* actions;          /* [n_act][horizon][n_envs] one-hot */
+    float* prob_out;         /* [n_act][horizon][n_envs] the probabilities the action was drawn from */
+    float* rewards;          /* [horizon][n_envs] */
+    uint8_t* dones;          /* [horizon][n_envs] */
+} rl_gridworld_gru_args;
+int rl_rollout_gridworld_gru(const rl_gridworld_gru_args* args, void* stream);
+
 /* prob[n_act][B] = softmax over the action axis of logits[n_act][B], max-subtracted; n_act <= 8. */
 int rl_categorical_softmax(size_t n_samples, int n_act, const float* logits, float* prob, void* stream);
 

@@ -34,7 +34,7 @@ SYMBOLS = [
     "rl_peer_mailbox_bytes", "rl_peer_alloc", "rl_peer_free", "rl_peer_export", "rl_peer_open", "rl_peer_close",
     "rl_peer_allreduce_sum",
     "rl_mlp_forward", "rl_mlp_forward_ws", "rl_mlp_backward", "rl_gaussian_head_workspace_bytes", "rl_gaussian_head", "rl_gaussian_fisher",
-    "rl_rollout_gridworld", "rl_categorical_softmax", "rl_categorical_head_workspace_bytes", "rl_categorical_head",
+    "rl_rollout_gridworld", "rl_rollout_gridworld_gru", "rl_categorical_softmax", "rl_categorical_head_workspace_bytes", "rl_categorical_head",
     "rl_categorical_fisher", "rl_cmaes_cov_update",
 ]
 
@@ -111,6 +111,21 @@ class GridWorldArgs(ctypes.Structure):
         ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("step_counter", ctypes.c_uint64),
         ("cell", ctypes.c_void_p), ("prob", ctypes.c_void_p), ("u", ctypes.c_void_p), ("state", ctypes.c_void_p),
         ("ts", ctypes.c_void_p), ("obs", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("prob_out", ctypes.c_void_p),
+        ("rewards", ctypes.c_void_p), ("dones", ctypes.c_void_p),
+    ]
+
+
+class GridWorldGruArgs(ctypes.Structure):
+    """Mirror of ``rl_gridworld_gru_args`` (include/rllab_amd.h): the fused GridWorld rollout of a CategoricalGRUPolicy."""
+    _fields_ = [
+        ("n_envs", ctypes.c_int32), ("horizon", ctypes.c_int32), ("max_path_length", ctypes.c_int32),
+        ("reset_at_start", ctypes.c_int32), ("n_row", ctypes.c_int32), ("n_col", ctypes.c_int32),
+        ("n_act", ctypes.c_int32), ("start_state", ctypes.c_int32), ("env_offset", ctypes.c_int32),
+        ("hidden", ctypes.c_int32), ("include_action", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("step_counter", ctypes.c_uint64),
+        ("cell", ctypes.c_void_p), ("theta", ctypes.c_void_p), ("u", ctypes.c_void_p), ("state", ctypes.c_void_p),
+        ("ts", ctypes.c_void_p), ("hidden_state", ctypes.c_void_p), ("prev_action", ctypes.c_void_p),
+        ("obs", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("prob_out", ctypes.c_void_p),
         ("rewards", ctypes.c_void_p), ("dones", ctypes.c_void_p),
     ]
 
@@ -284,6 +299,7 @@ def _load():
     lib.rl_gaussian_head.argtypes = [sz, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, f32, vp, vp, vp, sz, vp, vp]
     lib.rl_gaussian_fisher.argtypes = [sz, i32, vp, vp, vp, vp, f32, f32, vp, vp, vp]
     lib.rl_rollout_gridworld.argtypes = [ctypes.POINTER(GridWorldArgs), vp]
+    lib.rl_rollout_gridworld_gru.argtypes = [ctypes.POINTER(GridWorldGruArgs), vp]
     lib.rl_categorical_softmax.argtypes = [sz, i32, vp, vp, vp]
     lib.rl_categorical_head_workspace_bytes.restype = sz
     lib.rl_categorical_head_workspace_bytes.argtypes = []

@@ -30,6 +30,11 @@ def npo_inputs(policy, samples_data):
         cnt = torch.tensor(float(traj.count), dtype=torch.float64)
     else:
         cnt = D.all_reduce_sum_(w.to(torch.float64).sum())
+    if getattr(traj, "categorical", False) and getattr(policy, "recurrent", False):
+        # a recurrent categorical policy: the one-hot planes stay [., T, N] and the path starts ride along:
+        # (obs, actions, advantages, old_prob, start, weights, 1/W)
+        return (traj.obs, traj.actions, traj.advantages, traj.means, (traj.tin == 0), traj.valid.to(torch.float32),
+                (1.0 / cnt))
     if getattr(traj, "categorical", False):
         # a categorical policy: (obs, actions, advantages, old_prob, weights, 1/W) -- one-hot planes, recorded probabilities
         return (traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B), traj.advantages.reshape(B),
@@ -149,6 +154,19 @@ class NPO(BatchPolopt):
 
             def mean_kl(flat, obs, act, adv, old_prob, w, inv_count):  # noqa: F811
                 kl = dist.kl_sym(dict(prob=old_prob), _new_dist(flat, obs), axis=0)
+                return (kl * w).sum() * inv_count.to(kl.dtype)
+
+        if policy.recurrent and is_categorical(policy):
+            # both of the above apply (one GPU, whole paths); the closures are the recurrent ones on the "prob" planes
+            def surr_loss(flat, obs, act, adv, old_prob, start, w, inv_count):  # noqa: F811
+                new = policy.dist_info_planes(obs, act, start, flat)
+                lr = dist.likelihood_ratio_sym(act, dict(prob=old_prob), new, axis=0)
+                if trunc is not None:
+                    lr = torch.clamp(lr, max=trunc)
+                return -(lr * adv * w).sum() * inv_count.to(lr.dtype)
+
+            def mean_kl(flat, obs, act, adv, old_prob, start, w, inv_count):  # noqa: F811
+                kl = dist.kl_sym(dict(prob=old_prob), policy.dist_info_planes(obs, act, start, flat), axis=0)
                 return (kl * w).sum() * inv_count.to(kl.dtype)
 
         fused = None

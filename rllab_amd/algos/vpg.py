@@ -77,6 +77,20 @@ class VPG(BatchPolopt, Serializable):
                     max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
                 return float(mean_kl), float(max_kl)
 
+        if policy.recurrent and is_categorical(policy):
+            # both of the above apply (one GPU, whole paths); the closures are the recurrent ones on the "prob" planes
+            def surr_obj(flat, obs, act, adv, old_prob, start, w, inv_count):  # noqa: F811
+                logli = dist.log_likelihood_sym(act, policy.dist_info_planes(obs, act, start, flat), axis=0)
+                return -(logli * adv * w).sum() * inv_count.to(logli.dtype)
+
+            def f_kl(inputs):  # noqa: F811
+                obs, act, adv, old_prob, start, w, inv_count = inputs
+                with torch.no_grad():
+                    kl = dist.kl_sym(dict(prob=old_prob), policy.dist_info_planes(obs, act, start), axis=0)
+                    mean_kl = ((kl * w).sum() * inv_count.to(kl.dtype)).to(torch.float64)
+                    max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
+                return float(mean_kl), float(max_kl)
+
         fused = policy.fused_ops() if hasattr(policy, "fused_ops") and getattr(self, "use_fused", True) \
             and not policy.recurrent else None
         log_update_path(policy, fused)

@@ -27,6 +27,7 @@
 #include "../../include/rllab_amd.h"
 #include "capi_util.h"
 #include "device_rng.h"
+#include "gridworld_lane.h"
 
 namespace rl {
 
@@ -36,7 +37,6 @@ constexpr int CAT_THREADS = 256;
 constexpr int CAT_MAX_ACT = 8;
 constexpr int CAT_MAX_GRID = 1024;
 constexpr double CAT_TINY = 1e-8;
-constexpr int GRID_ACTIONS = 4;
 constexpr int GRID_MAX_STATES = 1024;
 constexpr int GRID_THREADS = 64;
 
@@ -60,33 +60,15 @@ __global__ void __launch_bounds__(GRID_THREADS) gridworld_rollout_kernel(rl_grid
         float u;
         if (a.u) u = a.u[col];
         else philox_draws<1, false>(&u, a.seed, (uint32_t)(a.env_offset + i), a.step_counter + (uint64_t)t, RNG_POLICY);
-        // weighted_sample: idx = sum(cumsum(p) < u), min(idx, n_act - 1); the running sum in float32, index order
-        float cs = p[0];
-        int act = cs < u ? 1 : 0;
-#pragma unroll
-        for (int k = 1; k < GRID_ACTIONS; ++k) {
-            cs = cs + p[k];
-            act += cs < u ? 1 : 0;
-        }
-        act = act > GRID_ACTIONS - 1 ? GRID_ACTIONS - 1 : act;
+        const int act = grid_weighted_sample(p, u);
 #pragma unroll
         for (int k = 0; k < GRID_ACTIONS; ++k) {
             a.actions[((size_t)k * T + t) * n + i] = (k == act) ? 1.0f : 0.0f;
             a.prob_out[((size_t)k * T + t) * n + i] = p[k];
         }
-        // get_possible_next_states: 0 left, 1 down, 2 right, 3 up; clipped at the border; a wall (or standing on a
-        // hole / the goal) leaves the state where it is
-        const int x = s / a.n_col, y = s % a.n_col;
-        int nx = x + (act == 1 ? 1 : (act == 3 ? -1 : 0));
-        int ny = y + (act == 2 ? 1 : (act == 0 ? -1 : 0));
-        nx = nx < 0 ? 0 : (nx > a.n_row - 1 ? a.n_row - 1 : nx);
-        ny = ny < 0 ? 0 : (ny > a.n_col - 1 ? a.n_col - 1 : ny);
-        int ns = nx * a.n_col + ny;
-        const int here = a.cell[s], there = a.cell[ns];
-        if (there == 1 || here == 2 || here == 3) ns = s;
-        const int kind = a.cell[ns];
-        bool done = kind == 2 || kind == 3;
-        const float reward = kind == 3 ? 1.0f : 0.0f;
+        bool done;
+        float reward;
+        const int ns = grid_transition(a.cell, a.n_row, a.n_col, s, act, done, reward);
         ts += 1;
         if (a.max_path_length > 0 && ts >= a.max_path_length) done = true;
         a.rewards[col] = reward;

@@ -6,7 +6,9 @@ Actions: 0 left, 1 down, 2 right, 3 up.  States and observations are the cell in
 are ``Discrete``.  ``GridWorldEnv`` is the host implementation in plain Python integers -- the oracle of the kernel.
 ``GridWorldVecEnv`` runs ``n`` copies on the device: observations are one-hot, so a policy is a function of the state
 index alone and the whole horizon of every env is ONE launch of ``rl_rollout_gridworld`` (csrc/categorical_kernels.hip)
-on the policy's probability table ``prob[n_act][n_states]``.
+on the policy's probability table ``prob[n_act][n_states]``.  A ``CategoricalGRUPolicy``'s probabilities depend on each
+env's hidden state: its rollout is ONE launch of ``rl_rollout_gridworld_gru`` (csrc/categorical_gru_kernels.hip), which takes
+a GRU step per env and step.
 """
 import ctypes
 
@@ -170,15 +172,19 @@ class GridWorldVecEnv(object):
                                   "rollout only: it has no per-transition device loop for other policies")
 
     def takes_rollout_of(self, policy):
+        from rllab_amd.policies.categorical_gru_policy import CategoricalGRUPolicy
         from rllab_amd.policies.categorical_mlp_policy import CategoricalMLPPolicy
+        if isinstance(policy, CategoricalGRUPolicy):
+            return (policy.obs_dim == self.n_states and policy.action_dim == 4 and policy.rollout_layout() is not None)
         return (isinstance(policy, CategoricalMLPPolicy) and policy.num_seq_inputs == 1
                 and policy.obs_dim == self.n_states and policy.action_dim == 4)
 
     def rollout(self, policy, horizon, reset_at_start=True, u=None):
-        """``horizon`` lock steps of sample -> step -> record -> auto-reset in ONE launch (rl_rollout_gridworld); returns
-        ``Trajectories`` whose ``means`` planes hold the recorded action probabilities.  ``u`` [T, n]: injected uniforms
-        (parity runs; otherwise each env's Philox stream).  ``reset_at_start=False``: the envs carry on from their
-        state and step count."""
+        """``horizon`` lock steps of sample -> step -> record -> auto-reset in ONE launch (rl_rollout_gridworld, or
+        rl_rollout_gridworld_gru for a CategoricalGRUPolicy); returns ``Trajectories`` whose ``means`` planes hold the
+        recorded action probabilities.  ``u`` [T, n]: injected uniforms (parity runs; otherwise each env's Philox
+        stream).  ``reset_at_start=False``: the envs carry on from their state and step count (and, under a recurrent
+        policy, from the hidden state and previous action the previous launch left on this executor)."""
         from rllab_amd import _lib
         from rllab_amd.sampler import dist as D
         from rllab_amd.sampler.trajectories import Trajectories
@@ -186,11 +192,10 @@ class GridWorldVecEnv(object):
             raise NotImplementedError("GridWorldVecEnv runs in one process on one GPU: the categorical path is not "
                                       "sharded over ranks")
         if not self.takes_rollout_of(policy):
-            raise NotImplementedError("the fused GridWorld rollout samples a CategoricalMLPPolicy (num_seq_inputs=1) built "
-                                      "on this env's spec")
+            why = policy.why_no_rollout_kernel() if hasattr(policy, "why_no_rollout_kernel") else None
+            raise NotImplementedError("the fused GridWorld rollout samples a CategoricalMLPPolicy (num_seq_inputs=1) or a "
+                                      "CategoricalGRUPolicy built on this env's spec%s" % ("" if why is None else ": " + why))
         T, n, S, A = int(horizon), self.n, self.n_states, 4
-        table = policy.prob_table()
-        assert table.shape == (A, S) and table.dtype == torch.float32 and table.is_contiguous() and table.device == self.device
         f32 = dict(dtype=torch.float32, device=self.device)
         if u is not None:
             u = torch.as_tensor(u, **f32).contiguous()
@@ -200,17 +205,39 @@ class GridWorldVecEnv(object):
         prob = torch.empty((A, T, n), **f32)
         rew = torch.empty((T, n), **f32)
         done = torch.empty((T, n), dtype=torch.uint8, device=self.device)
-        args = _lib.GridWorldArgs(
+        env_args = dict(
             n_envs=n, horizon=T, max_path_length=self.max_path_length, reset_at_start=int(bool(reset_at_start)),
             n_row=self.env.n_row, n_col=self.env.n_col, n_act=A, start_state=int(self.env.start_state),
             env_offset=self.env_offset, seed=self.seed, step_counter=self.step_counter,
-            cell=self.cell.data_ptr(), prob=table.data_ptr(), u=None if u is None else u.data_ptr(),
+            cell=self.cell.data_ptr(), u=None if u is None else u.data_ptr(),
             state=self.state.data_ptr(), ts=self.ts.data_ptr(), obs=obs.data_ptr(), actions=act.data_ptr(),
             prob_out=prob.data_ptr(), rewards=rew.data_ptr(), dones=done.data_ptr())
-        _lib.check(_lib.lib.rl_rollout_gridworld(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_gridworld")
+        recurrent = getattr(policy, "recurrent", False)
+        if recurrent:
+            # the hidden state [H, n] and the previous action index [n] are buffers of this executor next to ``state`` /
+            # ``ts``: written by every launch, read by one with ``reset_at_start=False``
+            H = policy.kernel_hidden
+            theta = policy.rollout_layout()
+            assert theta.dtype == torch.float32 and theta.is_contiguous() and theta.device == self.device
+            if getattr(self, "hidden_state", None) is None or tuple(self.hidden_state.shape) != (H, n):
+                if not reset_at_start:
+                    raise ValueError("rollout(reset_at_start=False) of a recurrent policy needs the hidden state a previous "
+                                     "launch of that policy left on this executor")
+                self.hidden_state = torch.zeros((H, n), **f32)
+                self.prev_action = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            args = _lib.GridWorldGruArgs(hidden=H, include_action=int(policy.state_include_action), theta=theta.data_ptr(),
+                                         hidden_state=self.hidden_state.data_ptr(),
+                                         prev_action=self.prev_action.data_ptr(), **env_args)
+            _lib.check(_lib.lib.rl_rollout_gridworld_gru(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_gridworld_gru")
+        else:
+            table = policy.prob_table()
+            assert table.shape == (A, S) and table.dtype == torch.float32 and table.is_contiguous() and table.device == self.device
+            args = _lib.GridWorldArgs(prob=table.data_ptr(), **env_args)
+            _lib.check(_lib.lib.rl_rollout_gridworld(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_gridworld")
         self.step_counter += T
         self._host_envs = None
-        return Trajectories(obs, act, prob, None, rew, done, self.max_path_length, categorical=True)
+        return Trajectories(obs, act, prob, None, rew, done, self.max_path_length, categorical=True,
+                            prev_action_info=bool(recurrent and policy.state_include_action))
 
     # -- plain VecEnv API: a host loop over the Python env ------------------------------------------------------------
     def _envs(self):
