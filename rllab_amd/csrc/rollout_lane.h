@@ -1,6 +1,7 @@
 // rollout_lane.h -- the per-lane pieces every env-per-lane kernel is made of: state planes in and out, reset and noise
 // draws (injected planes or the Philox streams), the observed observation, one Env::step under the launch's options, the
-// walking plane store, and the host-side check of an rl_env_cfg.  Shared by env_kernels.hip, population_kernels.hip and gru_kernels.hip.
+// walking plane store, and the host-side check of an rl_env_cfg.  Shared by env_kernels.hip and lane_rollout.h (the horizon
+// loop of population_kernels.hip and gru_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -82,7 +83,7 @@ __device__ __forceinline__ void step_one(float* s, const float* a, int normalize
 }
 
 // Env.step with the launch's options for the kernels that keep one env per lane and a per-lane policy next to it
-// (population_kernels.hip, gru_kernels.hip): step_one with the perturbation array ALWAYS handed to Env::step.
+// (lane_rollout.h): step_one with the perturbation array ALWAYS handed to Env::step.
 // step_cfg passes "no action noise" as a null pointer, and an array that is either null or live is addressed through
 // memory: the 4 * ACT + 4 bytes of scratch every env-per-lane kernel reports.  Here the array is always live and holds
 // -0.0f when the option is off -- the additive identity of IEEE addition for EVERY x, the zeros of either sign included
