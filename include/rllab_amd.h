@@ -425,6 +425,53 @@ typedef struct rl_gru_rollout_args {
 
 int rl_rollout_gaussian_gru(const rl_gru_rollout_args* args, void* stream);
 
+/* Recurrent population rollout: rl_rollout_population with a GaussianGRUPolicy per candidate -- the inner loop of CEM /
+ * CMA-ES on a recurrent policy, n_cand candidates x n_evals rollouts in one launch (rollout_population_gru_kernel<Env, H>,
+ * csrc/population_gru_kernels.hip).  Env i (n_envs = n_cand * n_evals) runs candidate i % n_cand, evaluation i / n_cand:
+ * it is reset, then stepped `horizon` times with auto-reset on the Philox streams of rl_rollout_population (the launch
+ * consumes horizon + 1 counters), its action mean coming from the GRU step of rl_rollout_gaussian_gru -- the same float32
+ * FMAs in the same order -- on ITS candidate's weights.  h starts at the candidate's own h0 and prev_action at zeros, at
+ * the reset and behind every done.
+ * theta_pop_T is the population TRANSPOSED: row p holds entry p of every candidate, the entries in the order of
+ * rl_gru_rollout_args.theta (log_std last) for `hidden` units and DI = obs_dim + (include_action ? act_dim : 0).
+ * The std of candidate c is (float)exp((double)max(log_std_c, log_min_std)).  first_path and the recording planes are
+ * those of rl_population_args.  hidden must be 32 or 64 (narrower layers: zero padding, exact); anything else is
+ * RL_ERR_UNSUPPORTED, as are the soft-constraint steps RL_CFG_LIMIT_MUJOCO / RL_CFG_CONTACT_MUJOCO of the legged envs. */
+typedef struct rl_population_gru_args {
+    int32_t kind;             /* rl_env_kind */
+    int32_t n_cand;           /* candidates: columns of theta_pop_T */
+    int32_t n_evals;          /* rollouts per candidate; n_envs = n_cand * n_evals */
+    int32_t horizon;          /* T: steps per env in this call */
+    int32_t max_path_length;  /* forced done when ts reaches it */
+    int32_t normalize;        /* NormalizedEnv action map on/off */
+    int32_t hidden;           /* 32 or 64 */
+    int32_t include_action;   /* state_include_action: x = [obs, prev_action]; 0 or 1 */
+    int32_t env_offset;       /* global index of env 0 (RNG key) */
+    float scale_reward;
+    float log_min_std;        /* log_std floor per candidate, log(min_std) */
+    int32_t reserved_pad;
+    double discount;
+    uint64_t seed;
+    uint64_t step_counter;    /* global step index of t = 0 (RNG counter base) */
+    float* state;             /* float[state_dim][n]  in/out (persisted solver state survives the reset) */
+    int32_t* ts;              /* int32[n]             out */
+    const float* theta_pop_T; /* float[P_pad][n_cand]: h0, (W_x, W_h, b) of r, u, c, W_out, b_out, log_std per column */
+    const float* eps;         /* NULL or float[act_dim][T][n] injected N(0,1) policy noise */
+    const float* reset_draws; /* NULL or float[T+1][reset_draws][n]: slice 0 = initial reset, slice t+1 = reset after step t */
+    const float* act_noise_z; /* NULL or float[T][act_dim][n] injected draws of the env's action noise */
+    const float* obs_noise_z; /* NULL or float[T+1][obs_dim][n] injected draws of the env's observation noise */
+    float* obs;               /* NULL or float[obs_dim][T][n] */
+    float* actions;           /* NULL or float[act_dim][T][n] */
+    float* means;             /* NULL or float[act_dim][T][n] */
+    float* rewards;           /* NULL or float[T][n] */
+    uint8_t* dones;           /* NULL or uint8[T][n] */
+    float* first_path;        /* float[3][n]: discounted return, undiscounted return, length of the first path */
+    const rl_env_cfg* cfg;    /* host; NULL = the env's defaults (its action_noise_z / obs_noise_z are not read here) */
+    const rl_launch_opts* opts;   /* host; NULL.  Reserved: the launch has one shape, 64 envs per single-wavefront workgroup */
+} rl_population_gru_args;
+
+int rl_rollout_population_gru(const rl_population_gru_args* args, void* stream);
+
 /* Segmented reverse linear-recurrence scans over [T][n] planes, fused:
  *   delta[t] = r[t] + gamma * V[t+1] * (1 - end[t]) - V[t]
  *   adv[t]   = delta[t] + gamma*lambda * (1 - end[t]) * adv[t+1]

@@ -26,7 +26,7 @@ ENV_INVERTED_DOUBLE_PENDULUM = 7
 # every symbol include/rllab_amd.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "rl_last_error", "rl_abi_version", "rl_env_query", "rl_env_terminates", "rl_env_action_bounds", "rl_env_default_cfg", "rl_vecenv_com",
-    "rl_vecenv_reset", "rl_vecenv_step", "rl_vecenv_step_graph", "rl_counter_add", "rl_vecenv_observe", "rl_rollout_gaussian_mlp", "rl_rollout_plan_query", "rl_rollout_lds_bytes", "rl_rollout_population", "rl_rollout_gaussian_gru", "rl_gae",
+    "rl_vecenv_reset", "rl_vecenv_step", "rl_vecenv_step_graph", "rl_counter_add", "rl_vecenv_observe", "rl_rollout_gaussian_mlp", "rl_rollout_plan_query", "rl_rollout_lds_bytes", "rl_rollout_population", "rl_rollout_gaussian_gru", "rl_rollout_population_gru", "rl_gae",
     "rl_discount_cumsum", "rl_debug_philox", "rl_policy_workspace_bytes", "rl_policy_activation_bytes", "rl_policy_loss_kl",
     "rl_policy_grad", "rl_policy_grad_loss", "rl_policy_fvp", "rl_policy_fvp_variant", "rl_policy_fvp_cg_step", "rl_cg_init", "rl_cg_step", "rl_trpo_step", "rl_line_search_point", "rl_line_search_decide", "rl_adam_step",
     "rl_path_scan", "rl_process_workspace_bytes", "rl_sample_stats_cols", "rl_sample_stats", "rl_adv_finish",
@@ -100,6 +100,12 @@ class GruRolloutArgs(ctypes.Structure):
         ("means", ctypes.c_void_p), ("rewards", ctypes.c_void_p), ("dones", ctypes.c_void_p),
         ("cfg", ctypes.POINTER(EnvCfg)), ("opts", ctypes.c_void_p),
     ]
+
+
+class PopulationGruArgs(ctypes.Structure):
+    """Mirror of ``rl_population_gru_args`` (include/rllab_amd.h): the fused rollout with one GaussianGRUPolicy per env --
+    the fields of ``PopulationArgs`` with ``include_action`` in the place of ``layer_activations``."""
+    _fields_ = [(("include_action" if f == "layer_activations" else f), t) for f, t in PopulationArgs._fields_]
 
 
 class GridWorldArgs(ctypes.Structure):
@@ -259,6 +265,7 @@ def _load():
                                          ctypes.POINTER(ctypes.c_size_t)]
     lib.rl_rollout_population.argtypes = [ctypes.POINTER(PopulationArgs), vp]
     lib.rl_rollout_gaussian_gru.argtypes = [ctypes.POINTER(GruRolloutArgs), vp]
+    lib.rl_rollout_population_gru.argtypes = [ctypes.POINTER(PopulationGruArgs), vp]
     lib.rl_gae.argtypes = [i32, i32, vp, vp, vp, f64, f64, vp, vp, vp, vp]
     lib.rl_discount_cumsum.argtypes = [i32, i32, vp, vp, f64, vp, vp]
     lib.rl_debug_philox.argtypes = [u32, u32, u32, u32, u32, u32, i32, vp, vp]

@@ -4,7 +4,8 @@ Per iteration: draw candidates  x_c = cur_mean + sample_std * N(0, I)  in parame
 the return of ``n_evals`` rollouts, refit mean and std of the sampling distribution to the best ``best_frac`` of them.
 
 The reference evaluates one candidate at a time (``_worker_rollout_policy``, :29-56: set_param_values, rollout).  Here a
-whole population is ONE launch of the population rollout (``HipVecEnv.rollout_population``, rl_rollout_population): env
+whole population is ONE launch of the population rollout (``HipVecEnv.rollout_population``, rl_rollout_population; for a
+GaussianGRUPolicy ``HipVecEnv.rollout_population_recurrent``, rl_rollout_population_gru -- ``population_launcher``): env
 i runs candidate i % n_cand with its own parameters, and the kernel hands back, per env, discounted return,
 undiscounted return and length of its first path -- everything the method needs.  Candidates are drawn, scored, sorted
 and refitted on the device in float64; one host read per iteration brings the logged values.
@@ -64,6 +65,7 @@ def population_why_unsupported(env, policy, plot=False):
     algorithms that evaluate candidates there: CEM, CMAES)."""
     from rllab_amd.envs.hip_env import HipEnv
     from rllab_amd.envs.normalized_env import NormalizedEnv
+    from rllab_amd.policies.gaussian_gru_policy import GaussianGRUPolicy
     from rllab_amd.policies.gaussian_mlp_policy import GaussianMLPPolicy, is_rectify
     from rllab_amd.policies.kernel_layout import tile_for
     from rllab_amd.sampler import dist as D
@@ -80,8 +82,11 @@ def population_why_unsupported(env, policy, plot=False):
         return "%s is not a HIP-native env (optionally wrapped in normalize)" % type(env).__name__
     if env._position_ids is not None:
         return "position_only observations: the candidates' first layers are built on the kept rows"
+    if isinstance(policy, GaussianGRUPolicy):
+        # the recurrent population rollout runs what the recurrent rollout runs
+        return policy.why_no_rollout_kernel()
     if not isinstance(policy, GaussianMLPPolicy):
-        return "%s is not a GaussianMLPPolicy" % type(policy).__name__
+        return "%s is neither a GaussianMLPPolicy nor a GaussianGRUPolicy" % type(policy).__name__
     if policy.state_dependent_std:
         return "the log-std is a network (adaptive_std / std_network): the population kernel takes one log_std row per candidate"
     if is_rectify(policy.hidden_nonlinearity):
@@ -93,6 +98,27 @@ def population_why_unsupported(env, policy, plot=False):
     if policy.kernel_layout() is None:
         return policy.why_no_kernel_layout()
     return None
+
+
+def population_launcher(policy, vec_env):
+    """``launch(xs, n_evals, horizon, discount, record) -> (Trajectories or None, first_path)``: candidates ``xs`` [n_cand, P]
+    (float64, the policy's parameter order) through the population rollout of this policy's family on ``vec_env`` --
+    ``rollout_population`` for a GaussianMLPPolicy, ``rollout_population_recurrent`` for a GaussianGRUPolicy (shared by
+    CEM and CMAES, behind ``population_why_unsupported``)."""
+    log_min_std = math.log(policy.min_std) if policy.min_std is not None else None
+    if getattr(policy, "recurrent", False):
+        def launch(xs, n_evals, horizon, discount, record):
+            return vec_env.rollout_population_recurrent(
+                policy.pack_rows(xs.to(torch.float32)), n_evals, horizon, discount, policy.kernel_hidden,
+                policy.state_include_action, record=record, log_min_std=log_min_std)
+        return launch
+    layout = policy.kernel_layout()
+
+    def launch(xs, n_evals, horizon, discount, record):
+        return vec_env.rollout_population(
+            layout.pack_rows(xs.to(torch.float32)), n_evals, horizon, discount, record=record,
+            layer_activations=layout.layer_activations, log_min_std=log_min_std)
+    return launch
 
 
 class CEM(RLAlgorithm, Serializable):
@@ -160,7 +186,7 @@ class CEM(RLAlgorithm, Serializable):
         reason = self.why_unsupported()
         if reason is not None:
             raise NotImplementedError("CEM: " + reason)
-        policy, layout = self.policy, self.policy.kernel_layout()
+        policy = self.policy
         dev = policy.flat_params.device
         seed = self.seed if self.seed is not None else ext.get_seed()
         if seed is None:
@@ -171,7 +197,7 @@ class CEM(RLAlgorithm, Serializable):
         # candidates of one launch: the population (criterion "paths"), or what batch_size needs if every path runs full length
         n_launch = int(self.n_samples) if self.batch_size is None else -(-int(self.batch_size) // mpl)
         vec_env = self.env.vec_env_executor(n_envs=n_launch * n_evals, max_path_length=mpl, seed=int(seed))
-        log_min_std = math.log(policy.min_std) if policy.min_std is not None else None
+        launch = population_launcher(policy, vec_env)
         f64 = dict(dtype=torch.float64, device=dev)
 
         cur_mean = torch.as_tensor(policy.get_param_values(), **f64)
@@ -184,10 +210,7 @@ class CEM(RLAlgorithm, Serializable):
             xs_l, fp_l, traj_l, n_used = [], [], [], None
             while n_used is None:
                 xs = torch.randn((n_launch, cur_mean.numel()), generator=gen, **f64) * sample_std + cur_mean
-                rows = layout.pack_rows(xs.to(torch.float32))
-                traj, first_path = vec_env.rollout_population(
-                    rows, n_evals, mpl, self.discount, record=bool(self.record_paths),
-                    layer_activations=layout.layer_activations, log_min_std=log_min_std)
+                traj, first_path = launch(xs, n_evals, mpl, self.discount, bool(self.record_paths))
                 xs_l.append(xs)
                 fp_l.append(first_path.view(3, n_evals, n_launch))
                 traj_l.append(traj)
@@ -252,6 +275,7 @@ class CEM(RLAlgorithm, Serializable):
         else:
             cat = lambda name, dim: torch.cat([getattr(c, name) for c in traj_l], dim=dim)
             traj = Trajectories(cat("obs", 2), cat("actions", 2), cat("means", 2), None, cat("rewards", 1), cat("dones", 1),
-                                traj_l[0].max_path_length, log_std_planes=cat("log_std_planes", 2))
+                                traj_l[0].max_path_length, log_std_planes=cat("log_std_planes", 2),
+                                prev_action_info=traj_l[0].prev_action_info)
         traj.valid = torch.cat(valid, dim=1)
         return PathList(traj)

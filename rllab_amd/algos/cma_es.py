@@ -13,14 +13,12 @@ Not built: what ``CMAState`` leaves out (bounds, transforms, injections, mirrors
 data logger); where the library would introduce a geno-pheno transform (max D / min D > 1e6) the run stops with
 ``conditioncov``.
 """
-import math
-
 import numpy as np
 import torch
 
 import rllab_amd.misc.logger as logger
 from rllab_amd.algos.base import RLAlgorithm
-from rllab_amd.algos.cem import CEM, cem_sample_prefix, population_why_unsupported
+from rllab_amd.algos.cem import CEM, cem_sample_prefix, population_launcher, population_why_unsupported
 from rllab_amd.algos.cma_state import CMAState
 from rllab_amd.core.serializable import Serializable
 from rllab_amd.misc import ext
@@ -95,13 +93,12 @@ class CMAES(RLAlgorithm, Serializable):
         reason = self.why_unsupported()
         if reason is not None:
             raise NotImplementedError("CMAES: " + reason)
-        policy, layout = self.policy, self.policy.kernel_layout()
+        policy = self.policy
         dev = policy.flat_params.device
         seed = self.seed if self.seed is not None else ext.get_seed()
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         mpl = int(self.max_path_length)
-        log_min_std = math.log(policy.min_std) if policy.min_std is not None else None
 
         cur_std = self.sigma0
         cur_mean = torch.as_tensor(policy.get_param_values(), dtype=torch.float64, device=dev)
@@ -111,6 +108,7 @@ class CMAES(RLAlgorithm, Serializable):
         # candidates of one launch: the population, or what batch_size needs if every path runs full length
         n_launch = es.sp.popsize if self.batch_size is None else max(-(-int(self.batch_size) // mpl), 1)
         vec_env = self.env.vec_env_executor(n_envs=n_launch, max_path_length=mpl, seed=int(seed))
+        launch = population_launcher(policy, vec_env)
         self.iteration_best, self.stop_dict = [], {}
 
         itr = 0
@@ -119,10 +117,7 @@ class CMAES(RLAlgorithm, Serializable):
             while n_used is None:
                 # Sample from multivariate normal distribution: every launch of one iteration from the same distribution
                 xs = es.ask(n_launch)
-                rows = layout.pack_rows(xs.to(torch.float32))
-                traj, first_path = vec_env.rollout_population(
-                    rows, 1, mpl, self.discount, record=bool(self.record_paths),
-                    layer_activations=layout.layer_activations, log_min_std=log_min_std)
+                traj, first_path = launch(xs, 1, mpl, self.discount, bool(self.record_paths))
                 xs_l.append(xs)
                 fp_l.append(first_path.view(3, 1, n_launch))
                 traj_l.append(traj)

@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(GRU_BLOCK) gridworld_gru_rollout_kernel(rl_gri
         const size_t col = (size_t)t * n + i;
         for (int k = 0; k < S; ++k) a.obs[((size_t)k * T + t) * n + i] = (k == s) ? 1.0f : 0.0f;
         float logit[GRID_ACTIONS], p[GRID_ACTIONS];
-        gru_cell<H, GRID_ACTIONS>(lanes.w, off, DI, OneHotInput<H>(S, s, include_action ? pa : -1), lanes.hc, lanes.hn, logit);
+        gru_cell<H, GRID_ACTIONS>(LdsWeights{lanes.w}, off, DI, OneHotInput<H>(S, s, include_action ? pa : -1), lanes.hc, lanes.hn, logit);
         lanes.swap();
         // max-subtracted float32 softmax, the sum in index order
         const float m = fmaxf(fmaxf(logit[0], logit[1]), fmaxf(logit[2], logit[3]));

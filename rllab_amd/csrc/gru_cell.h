@@ -1,10 +1,13 @@
-// gru_cell.h -- the one GRU step (rllab/core/network.py:150-155) of the env-per-lane recurrent rollouts, and what both of
-// them do around it.  Shared by gru_kernels.hip (dense input, Env::ACT means) and categorical_gru_kernels.hip (one-hot
-// input, four logits).
+// gru_cell.h -- the one GRU step (rllab/core/network.py:150-155) of the env-per-lane recurrent rollouts, and what they do
+// around it.  Shared by gru_kernels.hip (dense input, Env::ACT means), categorical_gru_kernels.hip (one-hot input, four
+// logits) and population_gru_kernels.hip (dense input, every lane its own weights).
 //
-// Weights: the same for every lane, staged ONCE per workgroup into LDS in the order they arrive in and read at
-// lane-uniform addresses (every lane the same address: one broadcast, no bank conflict), four output units per 16-byte
-// read.  The hidden state lives in LDS too, as two [H][64] tiles (lane l only ever touches column l: no bank conflict, no
+// Weights: the step takes them from a SOURCE, addressed by their offset (in floats) inside the parameter vector, four
+// consecutive ones per read.  LdsWeights: the same for every lane, staged ONCE per workgroup into LDS in the order they
+// arrive in and read at lane-uniform addresses (every lane the same address: one broadcast, no bank conflict), four output
+// units per 16-byte read.  RowWeights: one parameter vector per lane, read from the transposed population image
+// theta_pop_T[P][n_cand] -- entry e of every candidate is row e, so a read of the wavefront is one coalesced row segment.
+// The hidden state lives in LDS, as two [H][64] tiles (lane l only ever touches column l: no bank conflict, no
 // synchronisation): a step reads all of h from one tile while it writes h' into the other, then they swap.  The unit loop
 // runs at run time over blocks of GRU_UB units whose accumulators are named registers -- no register array is indexed at
 // run time, nothing of the policy is alive while an env steps.
@@ -13,6 +16,7 @@
 #include <math.h>
 #include "capi_util.h"
 #include "policy_mfma.h"
+#include "population_lane.h"
 
 namespace rl {
 
@@ -46,15 +50,43 @@ __device__ __forceinline__ F4 lds4(const float* p) {       // 16-byte aligned by
     return F4{{q.x, q.y, q.z, q.w}};
 }
 
+// the staged parameter vector in LDS, the same for every lane
+struct LdsWeights {
+    static constexpr int K_BLOCK = 1;         // hidden rows read ahead of their FMAs: an LDS broadcast is there at once
+    const float* w;
+    __device__ __forceinline__ F4 load4(int e) const { return lds4(w + e); }      // e a multiple of 4
+    __device__ __forceinline__ float load(int e) const { return w[e]; }
+};
+
+// this lane's column of theta_pop_T[P][n_cand]: entries e .. e + 3 are four consecutive rows (RowWalk: scalar row base +
+// the lane's 32-bit byte offset)
+struct RowWeights {
+    // hidden rows read ahead of their FMAs: a wavefront has its SIMD to itself and a row read comes from the memory side,
+    // so the 3 * GRU_UB * K_BLOCK reads of a block are all in flight before the first FMA waits for one
+    static constexpr int K_BLOCK = 8;
+    const float* theta_T;
+    size_t row_bytes;
+    mutable uint32_t lane_bytes;              // (RowWalk pins it to a vector register: not a value that changes)
+    __device__ __forceinline__ F4 load4(int e) const {
+        RowWalk r(theta_T, row_bytes, e);
+        F4 q;
+#pragma unroll
+        for (int u = 0; u < GRU_UB; ++u) q.v[u] = r.next(row_bytes, lane_bytes);
+        return q;
+    }
+    __device__ __forceinline__ float load(int e) const { return RowWalk(theta_T, row_bytes, e).next(row_bytes, lane_bytes); }
+};
+
 // x W_x* of a dense x = [o, prev_action]: float32 FMAs in the order of the input index
 template <int DO, int DA, int H>
 struct DenseInput {
     const float* o;
     const float* pa;
     bool include_action;
-    __device__ __forceinline__ void row(float x, int d, const float* xr, const float* xu, const float* xc, int j, F4& ar,
-                                        F4& au, F4& ax) const {
-        const F4 wr = lds4(xr + d * H + j), wu = lds4(xu + d * H + j), wc = lds4(xc + d * H + j);
+    template <class W>
+    __device__ __forceinline__ void row(const W& w, float x, int d, int xr, int xu, int xc, int j, F4& ar, F4& au,
+                                        F4& ax) const {
+        const F4 wr = w.load4(xr + d * H + j), wu = w.load4(xu + d * H + j), wc = w.load4(xc + d * H + j);
 #pragma unroll
         for (int u = 0; u < GRU_UB; ++u) {
             ar.v[u] = __builtin_fmaf(x, wr.v[u], ar.v[u]);
@@ -62,13 +94,13 @@ struct DenseInput {
             ax.v[u] = __builtin_fmaf(x, wc.v[u], ax.v[u]);
         }
     }
-    __device__ __forceinline__ void operator()(const float* xr, const float* xu, const float* xc, int j, F4& ar, F4& au,
-                                               F4& ax) const {
+    template <class W>
+    __device__ __forceinline__ void operator()(const W& w, int xr, int xu, int xc, int j, F4& ar, F4& au, F4& ax) const {
 #pragma unroll
-        for (int d = 0; d < DO; ++d) row(o[d], d, xr, xu, xc, j, ar, au, ax);
+        for (int d = 0; d < DO; ++d) row(w, o[d], d, xr, xu, xc, j, ar, au, ax);
         if (include_action) {
 #pragma unroll
-            for (int d = 0; d < DA; ++d) row(pa[d], DO + d, xr, xu, xc, j, ar, au, ax);
+            for (int d = 0; d < DA; ++d) row(w, pa[d], DO + d, xr, xu, xc, j, ar, au, ax);
         }
     }
 };
@@ -84,45 +116,58 @@ struct OneHotInput {
 #pragma unroll
         for (int u = 0; u < GRU_UB; ++u) a.v[u] = a.v[u] + b.v[u];
     }
-    __device__ __forceinline__ void operator()(const float* xr, const float* xu, const float* xc, int j, F4& ar, F4& au,
-                                               F4& ax) const {
-        add(ar, lds4(xr + row_s + j));
-        add(au, lds4(xu + row_s + j));
-        add(ax, lds4(xc + row_s + j));
+    template <class W>
+    __device__ __forceinline__ void operator()(const W& w, int xr, int xu, int xc, int j, F4& ar, F4& au, F4& ax) const {
+        add(ar, w.load4(xr + row_s + j));
+        add(au, w.load4(xu + row_s + j));
+        add(ax, w.load4(xc + row_s + j));
         if (pa >= 0) {
-            add(ar, lds4(xr + row_a + j));
-            add(au, lds4(xu + row_a + j));
-            add(ax, lds4(xc + row_a + j));
+            add(ar, w.load4(xr + row_a + j));
+            add(au, w.load4(xu + row_a + j));
+            add(ax, w.load4(xc + row_a + j));
         }
     }
 };
 
 // one GRU step of this lane: reads h from column `hc`, writes h' into column `hn`, returns out = h' W_out + b_out.
-// input(xr, xu, xc, j, ar, au, ax) adds x W_x* of units j .. j + GRU_UB into the three gate sums, behind the biases and
+// w: where the weights come from (LdsWeights, RowWeights), addressed by their offset inside the parameter vector.
+// input(w, xr, xu, xc, j, ar, au, ax) adds x W_x* of units j .. j + GRU_UB into the three gate sums, behind the biases and
 // ahead of the hidden units, which follow in index order.
-template <int H, int NOUT, class Input>
-__device__ __forceinline__ void gru_cell(const float* w, const GruLayout<H, NOUT>& off, int DI, const Input& input,
+template <int H, int NOUT, class W, class Input>
+__device__ __forceinline__ void gru_cell(const W& w, const GruLayout<H, NOUT>& off, int DI, const Input& input,
                                          const float* hc, float* hn, float* out) {
     static_assert(H % GRU_UB == 0, "unit blocks");
 #pragma unroll
-    for (int k = 0; k < NOUT; ++k) out[k] = w[off.b_out + k];
-    const float* xr = w + off.wx(0); const float* hr = w + off.wh(0, DI); const float* br = w + off.b(0, DI);
-    const float* xu = w + off.wx(1); const float* hu = w + off.wh(1, DI); const float* bu = w + off.b(1, DI);
-    const float* xc = w + off.wx(2); const float* hcw = w + off.wh(2, DI); const float* bc = w + off.b(2, DI);
-    const float* wo = w + off.w_out;
+    for (int k = 0; k < NOUT; ++k) out[k] = w.load(off.b_out + k);
+    const int xr = off.wx(0), hr = off.wh(0, DI), br = off.b(0, DI);
+    const int xu = off.wx(1), hu = off.wh(1, DI), bu = off.b(1, DI);
+    const int xc = off.wx(2), hcw = off.wh(2, DI), bc = off.b(2, DI);
+    const int wo = off.w_out;
 #pragma unroll 1
     for (int j = 0; j < H; j += GRU_UB) {
-        F4 ar = lds4(br + j), au = lds4(bu + j), ax = lds4(bc + j), ah = F4{{0.0f, 0.0f, 0.0f, 0.0f}};
-        input(xr, xu, xc, j, ar, au, ax);
-#pragma unroll 8
-        for (int k = 0; k < H; ++k) {
-            const float h = hc[k * WV];
-            const F4 wr = lds4(hr + k * H + j), wu = lds4(hu + k * H + j), wc = lds4(hcw + k * H + j);
+        F4 ar = w.load4(br + j), au = w.load4(bu + j), ax = w.load4(bc + j), ah = F4{{0.0f, 0.0f, 0.0f, 0.0f}};
+        input(w, xr, xu, xc, j, ar, au, ax);
+        constexpr int KB = W::K_BLOCK;            // rows read together; the FMAs follow in index order either way
+        static_assert(8 % KB == 0 && H % 8 == 0, "row blocks");
+#pragma unroll(8 / KB)
+        for (int k0 = 0; k0 < H; k0 += KB) {
+            float hk[KB];
+            F4 wr[KB], wu[KB], wc[KB];
 #pragma unroll
-            for (int u = 0; u < GRU_UB; ++u) {
-                ar.v[u] = __builtin_fmaf(h, wr.v[u], ar.v[u]);
-                au.v[u] = __builtin_fmaf(h, wu.v[u], au.v[u]);
-                ah.v[u] = __builtin_fmaf(h, wc.v[u], ah.v[u]);
+            for (int q = 0; q < KB; ++q) {
+                const int k = k0 + q;
+                hk[q] = hc[k * WV];
+                wr[q] = w.load4(hr + k * H + j); wu[q] = w.load4(hu + k * H + j); wc[q] = w.load4(hcw + k * H + j);
+            }
+#pragma unroll
+            for (int q = 0; q < KB; ++q) {
+                const float h = hk[q];
+#pragma unroll
+                for (int u = 0; u < GRU_UB; ++u) {
+                    ar.v[u] = __builtin_fmaf(h, wr[q].v[u], ar.v[u]);
+                    au.v[u] = __builtin_fmaf(h, wu[q].v[u], au.v[u]);
+                    ah.v[u] = __builtin_fmaf(h, wc[q].v[u], ah.v[u]);
+                }
             }
         }
 #pragma unroll
@@ -133,23 +178,36 @@ __device__ __forceinline__ void gru_cell(const float* w, const GruLayout<H, NOUT
             const float h_new = __builtin_fmaf(g, c, (1.0f - g) * h_old);
             hn[(j + u) * WV] = h_new;
             if constexpr (NOUT == GRU_UB) {                   // W_out[j + u][:] is one 16-byte read
-                const F4 q = lds4(wo + (j + u) * NOUT);
+                const F4 q = w.load4(wo + (j + u) * NOUT);
 #pragma unroll
                 for (int k = 0; k < NOUT; ++k) out[k] = __builtin_fmaf(h_new, q.v[k], out[k]);
             } else {
 #pragma unroll
-                for (int k = 0; k < NOUT; ++k) out[k] = __builtin_fmaf(h_new, wo[(j + u) * NOUT + k], out[k]);
+                for (int k = 0; k < NOUT; ++k) out[k] = __builtin_fmaf(h_new, w.load(wo + (j + u) * NOUT + k), out[k]);
             }
         }
     }
 }
 
-// This lane's view of the workgroup's dynamic LDS: the staged parameters and its column of the two hidden-state tiles.
+// This lane's column of the two [H][64] hidden-state tiles.
 template <int H>
-struct GruLanes {
-    const float* w;     // [w_floats]: theta, the same for every lane
+struct GruTiles {
     float* hc;          // column of the tile that holds h, what the next step reads
     float* hn;          // column of the tile the next step writes
+    template <class W>
+    __device__ __forceinline__ void fill_h0(const W& w) {       // h0: the first H entries of the parameter vector
+#pragma unroll 1
+        for (int k = 0; k < H; ++k) hc[k * WV] = w.load(k);
+    }
+    __device__ __forceinline__ void swap() { float* sw = hc; hc = hn; hn = sw; }
+};
+
+// This lane's view of the workgroup's dynamic LDS: the staged parameters and its column of the two hidden-state tiles.
+template <int H>
+struct GruLanes : GruTiles<H> {
+    using GruTiles<H>::hc;
+    using GruTiles<H>::hn;
+    const float* w;     // [w_floats]: theta, the same for every lane
     // every thread of the workgroup, before any of them leaves: stages theta[0 .. n_theta) and synchronises.
     // w_floats >= n_theta, a multiple of 4 (the tiles behind it stay 16-byte aligned).
     __device__ __forceinline__ GruLanes(const float* theta, int n_theta, int w_floats) {
@@ -160,10 +218,7 @@ struct GruLanes {
         hc = gru_smem + w_floats + threadIdx.x;
         hn = hc + H * WV;
     }
-    __device__ __forceinline__ void fill_h0() {
-#pragma unroll 1
-        for (int k = 0; k < H; ++k) hc[k * WV] = w[k];
-    }
+    __device__ __forceinline__ void fill_h0() { GruTiles<H>::fill_h0(LdsWeights{w}); }
     __device__ __forceinline__ void load(const float* plane, int n, int i) {      // plane [H][n]
 #pragma unroll 1
         for (int k = 0; k < H; ++k) hc[k * WV] = plane[(size_t)k * n + i];
@@ -172,7 +227,6 @@ struct GruLanes {
 #pragma unroll 1
         for (int k = 0; k < H; ++k) plane[(size_t)k * n + i] = hc[k * WV];
     }
-    __device__ __forceinline__ void swap() { float* sw = hc; hc = hn; hn = sw; }
 };
 
 // Launch `Kern(args, w_floats)`, one workgroup per 64 envs, with the LDS of a GruLayout<H, NOUT>(DI) + `extra` floats and

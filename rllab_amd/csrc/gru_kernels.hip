@@ -58,7 +58,7 @@ struct GruPolicy {
         for (int k = 0; k < DA; ++k) pa[k] = a.prev_action[(size_t)k * a.n + i];
     }
     __device__ __forceinline__ void mean(const float* o, float* m) {
-        gru_cell<H, DA>(lanes.w, off, DI, DenseInput<DO, DA, H>{o, pa, include_action}, lanes.hc, lanes.hn, m);
+        gru_cell<H, DA>(LdsWeights{lanes.w}, off, DI, DenseInput<DO, DA, H>{o, pa, include_action}, lanes.hc, lanes.hn, m);
         lanes.swap();
     }
     // policy.reset(dones): the next path starts from h0 with no previous action

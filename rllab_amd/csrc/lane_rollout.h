@@ -1,6 +1,6 @@
 // lane_rollout.h -- the horizon loop of the kernels that keep one continuous env per lane and a per-lane policy next to it:
 // get_action -> step -> record -> auto-reset for the whole horizon, made of the pieces of rollout_lane.h.  Shared by
-// population_kernels.hip and gru_kernels.hip, which supply the policy.
+// population_kernels.hip, gru_kernels.hip and population_gru_kernels.hip, which supply the policy.
 //
 // A policy is a struct with
 //   static constexpr bool RECORDS_ALL   true: the five output planes are all there (the entry point checked); false: each
@@ -38,7 +38,8 @@ struct LaneRolloutDev {
     EnvCfg cfg;
 };
 
-// the fields rl_population_args and rl_gru_rollout_args share by name -> LaneRolloutDev, with the checks both make
+// the fields rl_population_args, rl_gru_rollout_args and rl_population_gru_args share by name -> LaneRolloutDev, with the
+// checks all of them make
 template <class Env, class Args>
 static int lane_rollout_dev(const Args* g, long long n, const char* entry, const char* kernel, LaneRolloutDev& a) {
     // the widest plane [obs_dim][T][n] is addressed with size_t, a ROW of n floats with 32-bit byte offsets

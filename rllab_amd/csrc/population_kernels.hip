@@ -7,7 +7,7 @@
 // ITS candidate c = i % n_cand with plain float32 FMAs, and accumulates the returns of its env's first path.  The
 // population arrives transposed, theta_pop_T[P][n_cand], so lanes i, i + 1 read adjacent floats of one row: every weight
 // load of the wavefront is one coalesced row segment (two at the wrap of i % n_cand), addressed as scalar row base +
-// 32-bit lane offset.
+// 32-bit lane offset (RowWalk; it and the first-path sums live in population_lane.h, shared with population_gru_kernels.hip).
 //
 // Registers: the hidden activations h0 live in LDS as [H][64] floats (lane l only ever touches column l: no bank conflict,
 // no synchronisation), the unit loops run at run time over blocks of UB units whose accumulators are named registers --
@@ -21,6 +21,7 @@
 #include "envs.h"
 #include "lane_rollout.h"
 #include "policy_mfma.h"
+#include "population_lane.h"
 
 namespace rl {
 
@@ -33,24 +34,6 @@ struct PopulationDev : LaneRolloutDev {
     double discount;
     const float* theta_T;
     float* first_path;
-};
-
-// Rows of theta_pop_T read one after the other: the row address is a scalar that walks (one s_add_u32 / s_addc_u32 pair
-// per row), the load is the scalar-base + 32-bit lane offset form of global_load -- the reading twin of store_planes
-// (rollout_lane.h), for the same reason: P hoisted 64-bit row addresses fit no register file.
-struct RowWalk {
-    uintptr_t walk;
-    __device__ __forceinline__ RowWalk(const float* theta_T, size_t row_bytes, int row)
-        : walk(reinterpret_cast<uintptr_t>(theta_T) + (size_t)row * row_bytes) {}
-    __device__ __forceinline__ float next(size_t row_bytes, uint32_t& lane_bytes) {
-        typedef const __attribute__((address_space(1))) float* global_ptr;
-        asm volatile("" : "+s"(walk));
-        asm volatile("" : "+v"(lane_bytes));
-        const float v = *reinterpret_cast<global_ptr>(walk + lane_bytes);
-        walk += row_bytes;
-        return v;
-    }
-    __device__ __forceinline__ void skip(size_t bytes) { walk += bytes; }    // (wraps for a step back: unsigned arithmetic)
 };
 
 // mean = Wout^T act1(W1^T tanh(W0^T o + b0) + b1) + bout of this lane's candidate (network.py:36-101), float32 FMAs in the
@@ -118,10 +101,7 @@ struct PopulationPolicy {
     const size_t row_bytes;
     uint32_t cand_bytes;                      // byte offset of this env's candidate inside a row
     float std_[Env::ACT];
-    float ret_disc = 0.0f, ret_undisc = 0.0f;
-    double gpow = 1.0;                        // discount^t: float64, so the only float32 roundings are the sum's
-    int first_len = 0;
-    bool first_open = true;
+    FirstPath first;
 
     __device__ __forceinline__ PopulationPolicy(const PopulationDev& a_, int i, float* h0_)
         : a(a_), h0(h0_), row_bytes((size_t)a_.n_cand * sizeof(float)), cand_bytes((uint32_t)(i % a_.n_cand) * 4) {
@@ -137,15 +117,7 @@ struct PopulationPolicy {
     __device__ __forceinline__ void mean(const float* o, float* m) {
         population_forward<Env, H>(a.theta_T, row_bytes, cand_bytes, o, h0, a.ident1 != 0, m);
     }
-    __device__ __forceinline__ void stepped(const float*, float rs, bool d) {
-        if (first_open) {
-            ret_disc = __builtin_fmaf((float)gpow, rs, ret_disc);
-            ret_undisc += rs;
-            gpow *= a.discount;
-            first_len += 1;
-            first_open = !d;
-        }
-    }
+    __device__ __forceinline__ void stepped(const float*, float rs, bool d) { first.stepped(rs, d, a.discount); }
     __device__ __forceinline__ void finish(const float*) {}
 };
 
@@ -156,9 +128,7 @@ __global__ void __launch_bounds__(POP_BLOCK) rollout_population_kernel(Populatio
     if (i >= a.n) return;                     // no cross-lane traffic anywhere: the lanes past the last env just leave
     PopulationPolicy<Env, H> pol(a, i, h0_tile + threadIdx.x);
     rollout_lane<Env>(a, i, pol);
-    const float fp[3] = {pol.ret_disc, pol.ret_undisc, (float)pol.first_len};
-    uint32_t lane_f32 = (uint32_t)i * 4;
-    store_planes<3>(a.first_path, (size_t)a.n, lane_f32, fp);
+    pol.first.store(a.first_path, a.n, i);
 }
 
 template <class Env>

@@ -391,20 +391,56 @@ class HipVecEnv(object):
         ``log_std_planes`` (a [Da, 1, n] row broadcast over T, no copy).  ``layer_activations``: as ``KernelLayout.layer_activations``
         (tanh layers, or the identity second layer of a one-hidden-layer policy); ``log_min_std``: the floor of log_std
         (log(policy.min_std); None = no floor).  The injected planes are those of ``rollout`` (parity runs)."""
-        if self.position_ids is not None:
-            raise NotImplementedError("rollout_population on position_only observations: the candidates' first layers are "
-                                      "built on the kept rows")
-        T, n = int(horizon), self.n
+        n_cand, p_pad = self._population_shape("rollout_population", theta_pop, n_evals)
         do, da = self.q["obs_dim"], self.q["act_dim"]
-        assert torch.is_tensor(theta_pop) and theta_pop.is_cuda and theta_pop.dtype == torch.float32 and theta_pop.dim() == 2
-        n_cand, p_pad = int(theta_pop.shape[0]), int(theta_pop.shape[1])
-        if n_cand * int(n_evals) != n:
-            raise ValueError("rollout_population: %d candidates x %d evaluations on an executor of %d envs" % (
-                n_cand, int(n_evals), n))
         hidden = [H for H in (32, 64) if do * H + H + H * H + H + H * da + 2 * da == p_pad]
         if not hidden:
             raise NotImplementedError("rollout_population: rows of %d parameters are no (32, 32) / (64, 64) policy on this env "
                                       "(KernelLayout.pack_rows makes them)" % p_pad)
+        return self._launch_population(
+            _lib.PopulationArgs, _lib.lib.rl_rollout_population, "rl_rollout_population", theta_pop, n_evals, horizon, discount, record, eps, reset_draws,
+            action_noise_z, obs_noise_z, log_min_std, dict(hidden=hidden[0], layer_activations=int(layer_activations)))
+
+    def rollout_population_recurrent(self, theta_pop, n_evals, horizon, discount, hidden, include_action, record=True,
+                                     eps=None, reset_draws=None, action_noise_z=None, obs_noise_z=None, log_min_std=None):
+        """``rollout_population`` for a population of GaussianGRUPolicy candidates (rl_rollout_population_gru; CEM and
+        CMA-ES on a recurrent policy).  ``theta_pop``: [n_cand, P_pad] float32 device tensor, one candidate per row in the
+        layout of ``rollout_layout()`` for ``hidden`` = 32 or 64 units (``GRUPolicyBase.pack_rows``) with or without the
+        previous action in the input (``include_action``).  The same contract: ``n_cand * n_evals`` envs, env i runs
+        candidate ``i % n_cand`` from a reset -- ``h`` at the candidate's own ``h0``, no previous action, again behind every
+        done --, the step counter moves by ``horizon + 1``, ``record=False`` stores nothing but ``first_path``.  Returns
+        ``(Trajectories or None, first_path)``; the batch carries ``prev_action_info=include_action`` and every env's own
+        log_std row as ``log_std_planes``."""
+        n_cand, p_pad = self._population_shape("rollout_population_recurrent", theta_pop, n_evals)
+        do, da = self.q["obs_dim"], self.q["act_dim"]
+        H, di = int(hidden), do + (da if include_action else 0)
+        if H not in (32, 64) or H + 3 * (di * H + H * H + H) + H * da + 2 * da != p_pad:
+            raise NotImplementedError("rollout_population_recurrent: rows of %d parameters are no GRU of %d units on this env "
+                                      "with include_action=%r (GRUPolicyBase.pack_rows makes them)" % (
+                                          p_pad, H, bool(include_action)))
+        return self._launch_population(
+            _lib.PopulationGruArgs, _lib.lib.rl_rollout_population_gru, "rl_rollout_population_gru", theta_pop, n_evals, horizon, discount, record, eps,
+            reset_draws, action_noise_z, obs_noise_z, log_min_std, dict(hidden=H, include_action=int(bool(include_action))),
+            prev_action_info=bool(include_action))
+
+    def _population_shape(self, what, theta_pop, n_evals):
+        if self.position_ids is not None:
+            raise NotImplementedError("%s on position_only observations: the candidates' first layers are "
+                                      "built on the kept rows" % what)
+        assert torch.is_tensor(theta_pop) and theta_pop.is_cuda and theta_pop.dtype == torch.float32 and theta_pop.dim() == 2
+        n_cand, p_pad = int(theta_pop.shape[0]), int(theta_pop.shape[1])
+        if n_cand * int(n_evals) != self.n:
+            raise ValueError("%s: %d candidates x %d evaluations on an executor of %d envs" % (
+                what, n_cand, int(n_evals), self.n))
+        return n_cand, p_pad
+
+    def _launch_population(self, args_cls, launch, entry, theta_pop, n_evals, horizon, discount, record, eps, reset_draws,
+                           action_noise_z, obs_noise_z, log_min_std, policy_fields, prev_action_info=False):
+        """The launch both population rollouts share: ``args_cls`` / ``launch`` / ``entry`` are the C struct, the entry point and its name,
+        ``policy_fields`` the fields that describe the candidates' network."""
+        T, n = int(horizon), self.n
+        do, da = self.q["obs_dim"], self.q["act_dim"]
+        n_cand, p_pad = int(theta_pop.shape[0]), int(theta_pop.shape[1])
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         theta_T = theta_pop.t().contiguous()                      # [P_pad, n_cand]: lane i reads column i % n_cand
@@ -422,9 +458,9 @@ class HipVecEnv(object):
         oz = self._plane(obs_noise_z, (T + 1, do, n))
         lms = -1e30 if log_min_std is None else float(log_min_std)
         self._cfg_with(None, None)
-        args = _lib.PopulationArgs(
+        args = args_cls(
             kind=self.kind, n_cand=n_cand, n_evals=int(n_evals), horizon=T, max_path_length=self.max_path_length,
-            normalize=int(self.normalize), hidden=hidden[0], layer_activations=int(layer_activations),
+            normalize=int(self.normalize),
             env_offset=self.env_offset, scale_reward=self.scale_reward, log_min_std=lms, discount=float(discount),
             seed=self.seed, step_counter=self.step_counter,
             state=self.state.data_ptr(), ts=self.ts.data_ptr(), theta_pop_T=theta_T.data_ptr(),
@@ -434,15 +470,16 @@ class HipVecEnv(object):
             obs=None if obs is None else obs.data_ptr(), actions=None if act is None else act.data_ptr(),
             means=None if mean is None else mean.data_ptr(), rewards=None if rew is None else rew.data_ptr(),
             dones=None if done is None else done.data_ptr(), first_path=first_path.data_ptr(),
-            cfg=ctypes.pointer(self.cfg), opts=_lib.launch_opts())
-        _lib.check(_lib.lib.rl_rollout_population(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_population")
+            cfg=ctypes.pointer(self.cfg), opts=_lib.launch_opts(), **policy_fields)
+        _lib.check(launch(ctypes.byref(args), _lib.stream_ptr()), entry)
         self.step_counter += T + 1            # as rollout(): counter T belongs to the reset after the last step
         if not record:
             return None, first_path
         # every env's own (floored) log_std row, broadcast over time: what PathList / policy.log_diagnostics read
         ls = theta_pop[:, p_pad - da:].clamp_min(lms).t().repeat(1, int(n_evals))            # [Da, n]
         planes = ls.unsqueeze(1).expand(da, T, n)
-        return Trajectories(obs, act, mean, None, rew, done, self.max_path_length, log_std_planes=planes), first_path
+        return Trajectories(obs, act, mean, None, rew, done, self.max_path_length, log_std_planes=planes,
+                            prev_action_info=prev_action_info), first_path
 
 
 class HipEnv(Env, Serializable):

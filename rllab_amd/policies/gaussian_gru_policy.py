@@ -112,6 +112,13 @@ class GaussianGRUPolicy(GRUPolicyBase, StochasticPolicy, Serializable):
         if traj is not None and getattr(traj, "log_std_host", None) is not None:
             logger.record_tabular('AveragePolicyStd', float(np.mean(np.exp(traj.log_std_host))))
             return
+        if traj is not None and getattr(traj, "log_std_planes", None) is not None:
+            # a population's first paths: every env its own candidate's row (HipVecEnv.rollout_population_recurrent)
+            w = traj.valid.to(torch.float64) if getattr(traj, "valid", None) is not None else None
+            e = torch.exp(traj.log_std_planes.double())
+            val = float(e.mean()) if w is None else float((e * w).sum() / (w.sum() * e.shape[0]).clamp_min(1.0))
+            logger.record_tabular('AveragePolicyStd', val)
+            return
         logger.record_tabular('AveragePolicyStd', float(torch.exp(self.recorded_log_std().double()).mean()))
 
     # -- what the recurrent rollout kernel reads ----------------------------------------------------------------------

@@ -225,6 +225,17 @@ class GRUPolicyBase(object):
             off += rows_p * cols_p
         return np.concatenate(idx), off
 
+    def pack_rows(self, xs):
+        """Parameter ROWS [n_cand, P] (float32, device) -> kernel-layout rows [n_cand, P_pad], row c what
+        ``rollout_layout()`` holds after ``set_param_values(xs[c])``: zeros at the padded hidden units (a population of
+        candidates: ``HipVecEnv.rollout_population_recurrent``)."""
+        if self.hidden_dim == self.kernel_hidden:
+            return xs
+        idx, size = self.pad_index()
+        out = torch.zeros((xs.shape[0], size), dtype=xs.dtype, device=xs.device)
+        out.index_copy_(1, torch.as_tensor(idx, dtype=torch.long, device=xs.device), xs)
+        return out
+
     def rollout_layout(self):
         """The kernel's parameter vector (float32, device, refreshed when the parameters have moved), or None when the
         recurrent rollout kernel does not run this policy (``why_no_rollout_kernel()`` says why)."""
