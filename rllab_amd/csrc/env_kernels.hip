@@ -1010,12 +1010,21 @@ constexpr int QUAD_ENVS = 16;   // envs per wavefront
 #endif
 
 // COOP: the workgroup's wavefronts all carry the SAME group of envs (RolloutPolicyCoop); wavefront 0 stores
-template <class Pol, bool COOP = false>
+// PLAIN: the launch of a training run -- policy noise and reset draws from the in-kernel Philox streams, no action or
+// observation noise, no injected plane (launch_rollout takes this instantiation exactly when all of that holds).  The
+// option tests and every scalar only they need are then not part of the program: the argument block's pointers and
+// flags no longer crowd the loop's own scalars out of the scalar register file (the generic instantiation re-reads
+// 74 of them per env-step from the VGPR lanes they were spilled to).
+template <class Pol, bool COOP = false, bool PLAIN = false>
 __device__ __forceinline__ void swimmer_quad_body(const RolloutDev& a, const Pol& pol) {
     using Env = Swimmer;
     using Chain = Env::Chain;
 
     const int n = a.n, T = a.T;
+    // the options a PLAIN launch does not have, as constants
+    const float* const eps = PLAIN ? nullptr : a.eps;
+    const float* const reset_draws = PLAIN ? nullptr : a.reset_draws;
+    const float action_noise = PLAIN ? 0.0f : a.cfg.action_noise;
     const int lane = threadIdx.x & 63;
     const int wave_global = COOP ? (int)blockIdx.x : (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const int el = lane & (QUAD_ENVS - 1);            // env slot of this lane in the env-per-lane phases
@@ -1040,19 +1049,20 @@ __device__ __forceinline__ void swimmer_quad_body(const RolloutDev& a, const Pol
     int ts = a.ts[i];
     const size_t draws_slice = (size_t)Env::RESET_DRAWS * n;
     if (a.reset_at_start) {
-        reset_one<Env>(s, a.reset_draws, n, i, a.seed, env_global, a.step_counter, a.cfg);
+        reset_one<Env>(s, reset_draws, n, i, a.seed, env_global, a.step_counter, a.cfg);
         ts = 0;
     }
     float o[Env::OBS];
     float zq[Env::ACT] = {};      // policy noise of four steps, one step per replica group (lane-group shapes)
     Env::template observe<float>(s, o);
     const size_t obs_z_slice = (size_t)Env::OBS * n;
-    observed<Env>(o, a.cfg, a.obs_noise_z, n, i, a.seed, env_global, a.step_counter);
+    if constexpr (!PLAIN) observed<Env>(o, a.cfg, a.obs_noise_z, n, i, a.seed, env_global, a.step_counter);
 
-    // Output addressing: one uniform base per array, advanced by a row (n floats) per env-step, + a loop-invariant
-    // 32-bit byte offset per lane and plane in a VGPR (the dispatcher guarantees OBS * T * n * 4 < 2^32) -- a store is
-    // one instruction; the plane bases as 64-bit scalars would not fit the scalar register file next to the argument
-    // block and came back as ~45 v_readlane + 13 address adds per env-step.
+    // Output addressing: one uniform ROW POINTER per array, a 64-bit scalar that walks a row (n elements) per env-step
+    // -- one s_add_u32 / s_addc_u32 pair each, no t * n product per store group -- + a loop-invariant 32-bit byte offset
+    // per lane and plane in a VGPR (the dispatcher guarantees OBS * T * n * 4 < 2^32): a store is one instruction.  (The
+    // plane bases as 64-bit scalars would not fit the scalar register file and came back as ~45 v_readlane + 13 address
+    // adds per env-step.)
     uint32_t vo_obs[Env::OBS], vo_act[Env::ACT];
 #pragma unroll
     for (int k = 0; k < Env::OBS; ++k) {
@@ -1068,11 +1078,17 @@ __device__ __forceinline__ void swimmer_quad_body(const RolloutDev& a, const Pol
     asm volatile("" : "+v"(vo_row), "+v"(vo_done));
     // (the in-place asm keeps the zero-extension of the offset next to the add, which is what the back-end needs to
     //  select the scalar-base + 32-bit-offset form of global_store; it emits no instruction)
-    auto at = [](auto* base, size_t row_elems, uint32_t& byte_off) {
-        using P = decltype(base);
+    typedef __attribute__((address_space(1))) float* global_f32;
+    typedef __attribute__((address_space(1))) uint8_t* global_u8;
+    auto at = [](uintptr_t row_ptr, uint32_t& byte_off) {
         asm volatile("" : "+v"(byte_off));
-        return reinterpret_cast<P>(reinterpret_cast<char*>(base + row_elems) + byte_off);
+        return row_ptr + byte_off;
     };
+    // (integers, as the walk of store_planes: an asm operand of pointer type would lose its address space -- flat stores)
+    uintptr_t row_obs = reinterpret_cast<uintptr_t>(a.obs), row_act = reinterpret_cast<uintptr_t>(a.actions),
+              row_mean = reinterpret_cast<uintptr_t>(a.means), row_rew = reinterpret_cast<uintptr_t>(a.rewards),
+              row_done = reinterpret_cast<uintptr_t>(a.dones);
+    const size_t row_bytes = (size_t)n * sizeof(float);
 
     // lane-group state of the env, resident across env-steps (valid until a reset touches the wavefront)
     Chain::Lane<float> ls;
@@ -1081,17 +1097,13 @@ __device__ __forceinline__ void swimmer_quad_body(const RolloutDev& a, const Pol
     bool chain_valid = false;
 
     for (int t = 0; t < T; ++t) {
-        const size_t off = (size_t)t * n + i;
-        const size_t row = (size_t)t * n;            // uniform
-        if (live) {
-#pragma unroll
-            for (int k = 0; k < Env::OBS; ++k) *at(a.obs, row, vo_obs[k]) = o[k];
-        }
+        // (the walk stays a walk: a value in scalar registers, not t * n re-derived per store group)
+        asm volatile("" : "+s"(row_obs), "+s"(row_act), "+s"(row_mean), "+s"(row_rew), "+s"(row_done));
         float mean[Env::ACT], act[Env::ACT], z[Env::ACT];
         // (the noise first: its lane moves travel while the policy runs)
-        if (a.eps) {
+        if (eps) {
 #pragma unroll
-            for (int k = 0; k < Env::ACT; ++k) z[k] = a.eps[k * plane + off];
+            for (int k = 0; k < Env::ACT; ++k) z[k] = eps[k * plane + (size_t)t * n + i];
             landed<Env::ACT>(z);
         } else {
             // four steps' noise at once, one step per replica group (see rollout_kernel)
@@ -1103,17 +1115,22 @@ __device__ __forceinline__ void swimmer_quad_body(const RolloutDev& a, const Pol
         }
         pol.forward16(o, mean);
 #pragma unroll
-        for (int k = 0; k < Env::ACT; ++k) {
-            act[k] = __builtin_fmaf(z[k], std_[k], mean[k]);  // rnd * exp(log_std) + mean
-            if (live) {
-                *at(a.actions, row, vo_act[k]) = act[k];
-                *at(a.means, row, vo_act[k]) = mean[k];
+        for (int k = 0; k < Env::ACT; ++k) act[k] = __builtin_fmaf(z[k], std_[k], mean[k]);  // rnd * exp(log_std) + mean
+        // the observation, the action and its mean under ONE exec-mask bracket (the stores need no order among themselves;
+        // the observation is recorded here, while it is still in the registers the policy read it from)
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < Env::OBS; ++k) *reinterpret_cast<global_f32>(at(row_obs, vo_obs[k])) = o[k];
+#pragma unroll
+            for (int k = 0; k < Env::ACT; ++k) {
+                *reinterpret_cast<global_f32>(at(row_act, vo_act[k])) = act[k];
+                *reinterpret_cast<global_f32>(at(row_mean, vo_act[k])) = mean[k];
             }
         }
 
         // ---- Env.step: begin (env per lane) -> 50 sub-steps (lane group per env) -> end (env per lane) ----
         float eact[2], ctrl[3];
-        if (a.cfg.action_noise != 0.0f) {      // wave-uniform: MujocoEnv(action_noise=..) (mujoco_env.py:175-187)
+        if (action_noise != 0.0f) {      // wave-uniform: MujocoEnv(action_noise=..) (mujoco_env.py:175-187)
             float zn[Env::ACT], dact[Env::ACT];
             noise_draws<Env::ACT>(zn, a.act_noise_z ? a.act_noise_z + (size_t)t * Env::ACT * n : nullptr, n, i, a.seed,
                                   env_global, a.step_counter + (uint64_t)t, RNG_ACT_NOISE);
@@ -1178,18 +1195,20 @@ __device__ __forceinline__ void swimmer_quad_body(const RolloutDev& a, const Pol
         ts += 1;
         if (a.max_path_length > 0 && ts >= a.max_path_length) d = true;
         if (live) {
-            *at(a.rewards, row, vo_row) = r * a.scale_reward;
-            *at(a.dones, row, vo_done) = d ? 1 : 0;
+            *reinterpret_cast<global_f32>(at(row_rew, vo_row)) = r * a.scale_reward;
+            *reinterpret_cast<global_u8>(at(row_done, vo_done)) = d ? 1 : 0;
         }
+        row_obs += row_bytes; row_act += row_bytes; row_mean += row_bytes; row_rew += row_bytes; row_done += (size_t)n;
         if (d) {
-            const float* dr = a.reset_draws ? a.reset_draws + (size_t)(t + 1) * draws_slice : nullptr;
+            const float* dr = reset_draws ? reset_draws + (size_t)(t + 1) * draws_slice : nullptr;
             reset_one<Env>(s, dr, n, i, a.seed, env_global, a.step_counter + (uint64_t)t + 1, a.cfg);
             Env::template observe<float>(s, o);
             ts = 0;
         }
         if (__builtin_amdgcn_ballot_w64(d) != 0) chain_valid = false;     // some env of this wavefront starts afresh
-        observed<Env>(o, a.cfg, a.obs_noise_z ? a.obs_noise_z + (size_t)(t + 1) * obs_z_slice : nullptr, n, i, a.seed,
-                      env_global, a.step_counter + (uint64_t)t + 1);
+        if constexpr (!PLAIN)
+            observed<Env>(o, a.cfg, a.obs_noise_z ? a.obs_noise_z + (size_t)(t + 1) * obs_z_slice : nullptr, n, i, a.seed,
+                          env_global, a.step_counter + (uint64_t)t + 1);
     }
     if (live) {
         store_state<Env>(a.state, n, i, s);
@@ -1201,12 +1220,12 @@ __device__ __forceinline__ void swimmer_quad_body(const RolloutDev& a, const Pol
     }
 }
 
-template <int H, bool ACTS = false>
+template <int H, bool ACTS = false, bool PLAIN = false>
 __global__ void __launch_bounds__(LANE_TPB) rollout_swimmer_quad_kernel(RolloutDev a) {
     RolloutPolicy16<Swimmer, H, ACTS> pol;
     pol.init(a.theta);
     pol.act0 = a.act0; pol.act1 = a.act1;
-    swimmer_quad_body(a, pol);
+    swimmer_quad_body<RolloutPolicy16<Swimmer, H, ACTS>, false, PLAIN>(a, pol);
 }
 
 // the lane-group Swimmer under a wide / deep policy (RolloutPolicyWide::forward16: weight fragments in LDS)
@@ -2172,10 +2191,16 @@ static int launch_rollout(const rl_rollout_args* g, hipStream_t st) {
         default:
             if constexpr (std::is_same<Env, Swimmer>::value) {
                 if (pl.kernel == RL_ROLLOUT_SWIMMER_QUAD) {
-                    if (H == 32 && !acts) hipLaunchKernelGGL((rollout_swimmer_quad_kernel<32, false>), grid, block, 0, st, a);
-                    else if (H == 32) hipLaunchKernelGGL((rollout_swimmer_quad_kernel<32, true>), grid, block, 0, st, a);
-                    else if (!acts) hipLaunchKernelGGL((rollout_swimmer_quad_kernel<64, false>), grid, block, 0, st, a);
-                    else hipLaunchKernelGGL((rollout_swimmer_quad_kernel<64, true>), grid, block, 0, st, a);
+                    // the plain instantiation exactly when every option it leaves out is off (same plan either way)
+                    const bool plain = !a.eps && !a.reset_draws && !a.act_noise_z && !a.obs_noise_z &&
+                                       a.cfg.action_noise == 0.0f && a.cfg.obs_noise == 0.0f;
+#define RL_SWQ(HH, AA) do { if (plain) hipLaunchKernelGGL((rollout_swimmer_quad_kernel<HH, AA, true>), grid, block, 0, st, a); \
+                            else hipLaunchKernelGGL((rollout_swimmer_quad_kernel<HH, AA, false>), grid, block, 0, st, a); } while (0)
+                    if (H == 32 && !acts) RL_SWQ(32, false);
+                    else if (H == 32) RL_SWQ(32, true);
+                    else if (!acts) RL_SWQ(64, false);
+                    else RL_SWQ(64, true);
+#undef RL_SWQ
                     break;
                 }
                 if (pl.kernel == RL_ROLLOUT_SWIMMER_QUAD_COOP) {
