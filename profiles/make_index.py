@@ -31,6 +31,10 @@ RECIPES = [
     ("r06_c20_splith_ab_wide.txt", "fvp() of (20, 6) on (32, 32), 512 k samples: bf16 three-way against f16 two-way at one wavefront per SIMD", "tools/exp/r06_call20.sh"),
     ("r06_splith_*.csv", "SQ counter passes / FETCH_SIZE / kernel stats of the bf16 and the f16 split products, (32, 32) at 2.048 M and (64, 64) at 512 k samples", "tools/exp/r06_call19.sh"),
     ("curves/r06_splith_*", "learning under the f16 two-way and the bf16 three-way split products, same seeds; 1500-iteration soak", "tools/exp/r06_splith_curves.sh"),
+    ("fvp_lds_tr_ab_product.txt", "fvp() of the parent and the new library swapped in alternately, (13, 2) on (32, 32) at 2.048 M samples: the unit operands transposed through LDS, and two variants not kept",
+     "tools/exp/fvp_split_ab.py's loop with FVP_AB_WARM=400 FVP_AB_N=300 FVP_AB_READINGS=9, the parent as build/exp/lib_parent.so"),
+    ("fvp_lds_tr_ab_bench.txt", "headline bench lines of the parent and the new library, interleaved, and their --dump-outputs compared", "tools/exp/lib_ab.py 'python bench.py --gpus 1 --steps 20 --warmup 3'"),
+    ("fvp_lds_tr_*_pmc_product.csv", "one SQ counter pass over ten f16 split products at 2.048 M samples, parent / new library", "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE -- python tools/exp/fvp_splith_pmc.py 32"),
     ("r06_c11_policy_time.txt", "wide loss / gradient / product passes with (.orig) and without (lib_before_wpf) the one-tile-ahead prefetch", "tools/exp/r06_call11.sh"),
     ("r06_wide_kernel_bench.txt", "loss / gradient / product passes of the wide nets at the final sources", "python tools/kernel_bench.py --configs ..."),
     ("*_split_kernel_stats.csv", "kernel stats of the three Fisher-vector-product kernels back to back", "tools/prof_split.sh"),

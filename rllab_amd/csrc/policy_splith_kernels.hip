@@ -25,6 +25,7 @@
 #include "../../include/rllab_amd.h"
 #include "capi_util.h"
 #include "policy_mfma.h"
+#include "lds_tr_image.h"
 
 namespace rl {
 
@@ -34,6 +35,7 @@ namespace splith {
 
 typedef _Float16 f16;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -67,7 +69,7 @@ struct PA { f16x8 hi, lo, hs; };    // image: hi, lo = A - hi, hs = 2^-11 hi
 #define RL_ABL_SPLIT 0
 #endif
 #ifndef RL_ABL_TRANSPOSE
-#define RL_ABL_TRANSPOSE 0       // the transpositions left out (the parts are handed on as they are): what transposing LDS reads could buy at most
+#define RL_ABL_TRANSPOSE 0       // the transpositions still on the matrix pipe left out (the parts are handed on as they are)
 #endif
 
 __device__ __forceinline__ f32x16 mf(f16x8 a, f16x8 b, f32x16 c) {
@@ -221,6 +223,35 @@ __device__ __forceinline__ void transpose_units(const PB (&f)[2], const f16x8 (&
     d = mf(f[1].lo, Id[1], d);
     pack_exact(d, out[0].lo, out[1].lo);
 }
+// The same transposition through LDS (lds_tr_image.h): the sample-major parts go into a wave-private 4 KB image, one
+// 16-byte store per part and k-block, and come back unit-major by ds_read_b64_tr_b16, two per part and k-block -- no matrix
+// instruction, no repacking.  Lane (unit lj, half lh) receives in element j of k-block kb the value of sample
+// frag_unit(8 kb + j, lh): the assignment transpose_units + pack_exact produce, so the products that follow see the same
+// operands in the same k positions and the same bits come out.  The image is a wavefront's own and its LDS queue is in
+// order: wave_sync() (compiler only) between the stores and the reads of one operand, and between the reads of one and the
+// stores of the next into the same 4 KB.  The reads gather across lanes: EXEC must be all ones, so they stay in
+// wave-uniform control flow and every lane's address lies inside the image.
+__device__ __forceinline__ void tr_store(char* w, const PB (&f)[2]) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        *reinterpret_cast<f16x8*>(w + lds_tr::TR_KB_STORE * kb) = f[kb].hi;
+        *reinterpret_cast<f16x8*>(w + lds_tr::TR_PART_BYTES + lds_tr::TR_KB_STORE * kb) = f[kb].lo;
+    }
+}
+__device__ __forceinline__ f16x8 tr_read8(const char* r) {
+    typedef short v4i16 __attribute__((vector_size(8)));
+    typedef __attribute__((address_space(3))) v4i16* lp_t;
+    const f16x4 t0 = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)r));
+    const f16x4 t1 = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(r + lds_tr::TR_T_READ)));
+    return __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+__device__ __forceinline__ void tr_load(const char* r, PB (&out)[2]) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        out[kb].hi = tr_read8(r + lds_tr::TR_KB_READ * kb);
+        out[kb].lo = tr_read8(r + lds_tr::TR_PART_BYTES + lds_tr::TR_KB_READ * kb);
+    }
+}
 template <int KB0>
 __device__ __forceinline__ void transpose_inputs(const PB (&f)[KB0], const f16x8 (&Idx)[KB0], PB (&out)[2]) {
 #if RL_ABL_TRANSPOSE
@@ -371,7 +402,8 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
     constexpr int KB0 = (DO + 1 + 15) / 16;
     constexpr int N_OPS = ops_count(KB0), OPS_BYTES = ops_bytes(KB0);
     constexpr int TAILV = 16 * DA * 2 + 16;        // floats per lane half: W2 rows | dW2~ rows | db1~
-    constexpr int SPILL_BYTES = 2 * 2 * WV * 16;   // a wavefront's h0 parts wait here for the back-propagation
+    constexpr int SPILL_BYTES = 2 * lds_tr::TR_PART_BYTES;   // a wavefront's transposition image: h0's parts wait here for the
+                                                             // back-propagation, then gz1~'s and gz0~'s pass through (tr_store)
     constexpr int XPIECES = (DO + 1 + 7) / 8;
     constexpr int XLAND_BYTES = XPIECES * WV * 16;
     constexpr int WAVE_BYTES = LAND_BYTES + SPILL_BYTES + XLAND_BYTES;
@@ -384,6 +416,8 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
     char* const land = smem + wave * WAVE_BYTES;
     char* const spill = land + LAND_BYTES;
     char* const xland = spill + SPILL_BYTES;
+    char* const tr_w = spill + lds_tr::tr_store_lane(lane);            // this lane's store into / transposed read from the image
+    const char* const tr_r = spill + lds_tr::tr_read_lane(lane);
     char* const ops = smem + WAVES * WAVE_BYTES;                       // [N_OPS][3][64] x 16 B
     float* const tailv = reinterpret_cast<float*>(ops + OPS_BYTES);    // [2][TAILV]
     float* const red = tailv + 2 * TAILV;
@@ -503,14 +537,11 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
         }
         return acc_;
     };
-    f16x8 Id[2], Idx[KB0];
+    f16x8 Idx[KB0];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        Id[0][j] = (f16)(frag_unit(j, lh) == lj ? 1.0f : 0.0f);
-        Id[1][j] = (f16)(frag_unit(8 + j, lh) == lj ? 1.0f : 0.0f);
+    for (int j = 0; j < 8; ++j)
 #pragma unroll
         for (int kb = 0; kb < KB0; ++kb) Idx[kb][j] = (f16)(16 * kb + 8 * lh + j == lj ? XT_SCALE : 0.0f);
-    }
 
     // ---- accumulators ---------------------------------------------------------------------------------------------
     f32x16 gW1, gW0, gW1c, gW0c;
@@ -578,11 +609,8 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = tv[2 * DA * 16 + r];       // db1~
         acc = chain_ahead(KB0, 2, H0s, acc, opcur, KB0 + 2);             // dW1~^T h0
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            *reinterpret_cast<f16x8*>(spill + ((kb * 2 + 0) * WV + lane) * 16) = H0s[kb].hi;
-            *reinterpret_cast<f16x8*>(spill + ((kb * 2 + 1) * WV + lane) * 16) = H0s[kb].lo;
-        }
+        wave_sync();                 // (the image's last reader was the previous tile's G0t)
+        tr_store(tr_w, H0s);
         stage();
         {
             PB D0s[2];
@@ -655,21 +683,32 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
         stage();
         opcur = op(KB0 + 4);
         __builtin_amdgcn_sched_barrier(0);
-        PB G1s[2];
+        PB G1s[2], H0t[2], G1t[2];
         split_frag(gz1, G1s);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
         acc = chain_ahead(KB0 + 4, 2, G1s, acc, opcur, -1);              // W1~ gz1~
+        // the image in sequence: h0 (stored in the tangent pass) -> H0t, gz1~ -> G1t, gz0~ -> G0t.  The reads of an operand
+        // are issued together and ahead of independent work: gz0~ and its split run over the round trip of H0t / G1t,
+        // gW1's product over that of G0t.
+        wave_sync();
+        tr_load(tr_r, H0t);
+        wave_sync();
+        tr_store(tr_w, G1s);
+        wave_sync();
+        tr_load(tr_r, G1t);
+        __builtin_amdgcn_sched_barrier(0);      // (left alone, the scheduler sinks the reads to their first use)
         stage();
+        f32x16 gz0;
+        times_dtanh(acc, h0, gz0, S.kg);
         {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                H0s[kb].hi = *reinterpret_cast<const f16x8*>(spill + ((kb * 2 + 0) * WV + lane) * 16);
-                H0s[kb].lo = *reinterpret_cast<const f16x8*>(spill + ((kb * 2 + 1) * WV + lane) * 16);
-            }
-            PB H0t[2], G1t[2];
-            transpose_units(H0s, Id, H0t);
-            transpose_units(G1s, Id, G1t);
+            PB G0s[2], G0t[2], Xt[2];
+            split_frag(gz0, G0s);
+            wave_sync();
+            tr_store(tr_w, G0s);
+            wave_sync();
+            tr_load(tr_r, G0t);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {                              // gW1 += h0^T gz1~ (samples are K)
 #if RL_SPLITH_TWO_ACC
@@ -678,13 +717,6 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
                 gW1 = mm_ab(as_image(H0t[kb]), G1t[kb], gW1);
 #endif
             }
-        }
-        f32x16 gz0;
-        times_dtanh(acc, h0, gz0, S.kg);
-        {
-            PB G0s[2], G0t[2], Xt[2];
-            split_frag(gz0, G0s);
-            transpose_units(G0s, Id, G0t);
             transpose_inputs<KB0>(Xs, Idx, Xt);
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {                              // gW0 += x~_ext^T gz0~
