@@ -425,6 +425,53 @@ typedef struct rl_gru_rollout_args {
 
 int rl_rollout_gaussian_gru(const rl_gru_rollout_args* args, void* stream);
 
+/* The update of a GaussianGRUPolicy on the dense planes of a recurrent batch (csrc/gru_bptt_kernels.hip): surrogate loss
+ * and mean KL of TRPO / TNPG, the flat gradient of the loss by back-propagation through time, and the product of the
+ * Fisher matrix (the Hessian of the mean KL at new == old) with a vector.  Sample s = t * n_envs + i is step t of env
+ * column i; at t = 0 and wherever start[s] != 0 the step's input state is h0 and prev_action = 0 (elsewhere prev_action is
+ * actions[t - 1]), and no gradient or tangent crosses it.  theta, grad, v and out have the layout of
+ * rl_gru_rollout_args.theta (log_std last); h0 is not trainable: its entries of grad / out are 0.
+ *   loss = - sum_s w lr adv / W,  lr = p_theta(a | .) / p_old(a | .);    kl = sum_s w KL(old || theta) / W
+ * with the formulas of the reference's DiagonalGaussian (its 1e-8 in the KL's denominator included), 1 / W = inv_count.
+ * hidden must be 32 or 64 (narrower layers: zero padding, exact) and (obs_dim, act_dim) one of (4, 1), (6, 1), (13, 2),
+ * (20, 6); anything else, and a shape whose parameters, tangent vector and state tiles exceed the LDS of a CU, is
+ * RL_ERR_UNSUPPORTED before anything is launched (rl_last_error has the width / the byte count). */
+typedef struct rl_gru_batch {
+    int32_t n_envs;           /* N: env columns */
+    int32_t horizon;          /* T: rows; T * N < 2^31 */
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t hidden;           /* 32 or 64 */
+    int32_t include_action;   /* state_include_action: x = [obs, prev_action] */
+    double inv_count;         /* 1 / W */
+    const float* theta;       /* device */
+    const float* obs;         /* float[obs_dim][T][N] */
+    const float* actions;     /* float[act_dim][T][N] */
+    const float* advantages;  /* float[T][N] */
+    const float* old_means;   /* float[act_dim][T][N] */
+    const float* old_log_std; /* float[act_dim] */
+    const uint8_t* start;     /* uint8[T][N]: a path starts here (row 0 starts one in every column whatever it holds) */
+    const float* weights;     /* float[T][N] */
+    float* means;             /* NULL, or float[act_dim][T][N]: the means rl_gru_gaussian_eval / _grad compute */
+    void* workspace;          /* device, rl_gru_workspace_bytes; one batch at a time */
+    size_t workspace_bytes;
+} rl_gru_batch;
+
+/* Bytes of rl_gru_batch.workspace; 0 (and rl_last_error) for a shape the kernels are not built for or that does not fit. */
+size_t rl_gru_workspace_bytes(int n_envs, int horizon, int obs_dim, int act_dim, int hidden, int include_action);
+/* out2 (device, 2 doubles) <- loss, kl: one forward sweep. */
+int rl_gru_gaussian_eval(const rl_gru_batch* batch, double* out2, void* stream);
+/* out2 <- loss, kl (the bits of rl_gru_gaussian_eval) and grad (device, float[P]) <- d loss / d theta: a forward sweep
+ * that leaves h of every step in the workspace, a backward sweep over t = T - 1 .. 0, and the weight gradient's sums over
+ * the samples on the matrix cores, added in a fixed order (no atomics: the same bits every run). */
+int rl_gru_gaussian_grad(const rl_gru_batch* batch, double* out2, float* grad, void* stream);
+/* out (device, float[P]) <- F v.  Reads the h planes rl_gru_gaussian_grad left in the SAME workspace for the same batch
+ * at the same theta: call that first, and again whenever theta (which callers update in place) or the batch changes.
+ * The library cannot see either change, so a product on stale planes is WRONG WITHOUT AN ERROR -- the contract of
+ * rl_policy_batch.activations between rl_policy_grad and rl_policy_fvp; policies/fused_gru_ops.py keys the planes on
+ * (batch tensors, parameter version) and runs the gradient pass itself when they do not match. */
+int rl_gru_gaussian_fvp(const rl_gru_batch* batch, const float* v, float* out, void* stream);
+
 /* Recurrent population rollout: rl_rollout_population with a GaussianGRUPolicy per candidate -- the inner loop of CEM /
  * CMA-ES on a recurrent policy, n_cand candidates x n_evals rollouts in one launch (rollout_population_gru_kernel<Env, H>,
  * csrc/population_gru_kernels.hip).  Env i (n_envs = n_cand * n_evals) runs candidate i % n_cand, evaluation i / n_cand:
