@@ -472,6 +472,48 @@ int rl_gru_gaussian_grad(const rl_gru_batch* batch, double* out2, float* grad, v
  * (batch tensors, parameter version) and runs the gradient pass itself when they do not match. */
 int rl_gru_gaussian_fvp(const rl_gru_batch* batch, const float* v, float* out, void* stream);
 
+/* The update of a CategoricalGRUPolicy on the dense planes of a recurrent GridWorld batch
+ * (csrc/categorical_gru_bptt_kernels.hip): the three passes of rl_gru_gaussian_* for prob = softmax(GRU) over n_act = 4
+ * actions on one-hot inputs.  The one-hot observation and action planes enter as INDEX planes (state: the argmax of the
+ * observation, action: the argmax of the action); both are clamped into range.  At t = 0 and wherever start[s] != 0 the
+ * step's input state is h0 with no previous action.  theta, grad, v and out have the layout of
+ * rl_gridworld_gru_args.theta for `hidden` units and DI = n_states + (include_action ? 4 : 0); h0 is not trainable: its
+ * entries of grad / out are 0.
+ *   loss = - sum_s w lr adv / W,  lr = (p[a] + 1e-8) / (p_old[a] + 1e-8)
+ *   kl   = sum_s w sum_k p_old[k] (log(p_old[k] + 1e-8) - log(p[k] + 1e-8)) / W          (1 / W = inv_count)
+ * in float64 on the float32 probabilities of the rollout's own softmax: at unchanged parameters `prob` is the plane
+ * rl_rollout_gridworld_gru recorded, bit for bit, and kl is exactly 0.  The Fisher matrix is the Hessian of kl at
+ * new == old with the 1e-8 kept (rl_categorical_fisher).  hidden must be 32 or 64 (narrower layers: zero padding, exact);
+ * another width, and a map whose parameters, tangent vector and state tiles exceed the LDS of a CU (4x4 at 64 units:
+ * 182304 bytes), is RL_ERR_UNSUPPORTED before anything is launched (rl_last_error has the width / the byte count). */
+typedef struct rl_gru_categorical_batch {
+    int32_t n_envs;           /* N: env columns */
+    int32_t horizon;          /* T: rows; T * N < 2^31 */
+    int32_t n_states;         /* S: the one-hot observation's width */
+    int32_t n_act;            /* must be 4 */
+    int32_t hidden;           /* 32 or 64 */
+    int32_t include_action;   /* state_include_action: x = [onehot(state), onehot(prev_action)]; 0 or 1 */
+    double inv_count;         /* 1 / W */
+    const float* theta;       /* device */
+    const int32_t* state;     /* int32[T][N] */
+    const int32_t* action;    /* int32[T][N] */
+    const float* advantages;  /* float[T][N] */
+    const float* old_prob;    /* float[4][T][N] */
+    const uint8_t* start;     /* uint8[T][N]: a path starts here (row 0 starts one in every column whatever it holds) */
+    const float* weights;     /* float[T][N] */
+    float* prob;              /* NULL, or float[4][T][N]: the probabilities rl_gru_categorical_eval / _grad compute */
+    void* workspace;          /* device, rl_gru_categorical_workspace_bytes; one batch at a time */
+    size_t workspace_bytes;
+} rl_gru_categorical_batch;
+
+/* Bytes of rl_gru_categorical_batch.workspace; 0 (and rl_last_error) for a shape that is not built or does not fit. */
+size_t rl_gru_categorical_workspace_bytes(int n_envs, int horizon, int n_states, int hidden, int include_action);
+/* The contracts of rl_gru_gaussian_eval / _grad / _fvp: out2 (device, 2 doubles) <- loss, kl; grad (device, float[P]);
+ * _fvp reads the h planes _grad left in the SAME workspace for the same batch at the same theta. */
+int rl_gru_categorical_eval(const rl_gru_categorical_batch* batch, double* out2, void* stream);
+int rl_gru_categorical_grad(const rl_gru_categorical_batch* batch, double* out2, float* grad, void* stream);
+int rl_gru_categorical_fvp(const rl_gru_categorical_batch* batch, const float* v, float* out, void* stream);
+
 /* Recurrent population rollout: rl_rollout_population with a GaussianGRUPolicy per candidate -- the inner loop of CEM /
  * CMA-ES on a recurrent policy, n_cand candidates x n_evals rollouts in one launch (rollout_population_gru_kernel<Env, H>,
  * csrc/population_gru_kernels.hip).  Env i (n_envs = n_cand * n_evals) runs candidate i % n_cand, evaluation i / n_cand:

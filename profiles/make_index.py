@@ -16,6 +16,8 @@ RECIPES = [
      "profiles/run_profile.sh <tag> (traffic step: profiles/summarize.py traffic ...)"),
     ("gru_bptt_time.json", "loss + KL, gradient and Fisher-vector product of a GaussianGRUPolicy per call, and one whole TRPO update: the recurrent update kernels next to the float32 autograd closures, the sampler's batch for 4096 Cartpole envs, max_path_length 100 (105 rows x 4096 columns), 32 units",
      "python tools/exp/gru_bptt_time.py --out profiles/gru_bptt_time.json"),
+    ("categorical_gru_bptt_time.json", "loss + KL, gradient and Fisher-vector product of a CategoricalGRUPolicy per call, and one whole TRPO update: the recurrent categorical update kernels next to the float32 autograd closures, the sampler's batch for 4096 GridWorld 4x4 envs, max_path_length 100, 32 units",
+     "python tools/exp/categorical_gru_bptt_time.py --out profiles/categorical_gru_bptt_time.json"),
     ("*_bench_line.json", "the default bench line of that tree", "python bench.py"),
     ("*_bench_under_rocprof.log", "bench stdout under the kernel-trace pass", "profiles/run_profile.sh <tag>"),
     ("*_c5_kernel_stats.csv", "kernel stats of C5's per-GPU shard", "profiles/run_profile.sh <tag> cheetah1024_trpo_gae"),

@@ -27,7 +27,9 @@ ENV_INVERTED_DOUBLE_PENDULUM = 7
 SYMBOLS = [
     "rl_last_error", "rl_abi_version", "rl_env_query", "rl_env_terminates", "rl_env_action_bounds", "rl_env_default_cfg", "rl_vecenv_com",
     "rl_vecenv_reset", "rl_vecenv_step", "rl_vecenv_step_graph", "rl_counter_add", "rl_vecenv_observe", "rl_rollout_gaussian_mlp", "rl_rollout_plan_query", "rl_rollout_lds_bytes", "rl_rollout_population", "rl_rollout_gaussian_gru",
-    "rl_gru_workspace_bytes", "rl_gru_gaussian_eval", "rl_gru_gaussian_grad", "rl_gru_gaussian_fvp", "rl_rollout_population_gru", "rl_gae",
+    "rl_gru_workspace_bytes", "rl_gru_gaussian_eval", "rl_gru_gaussian_grad", "rl_gru_gaussian_fvp",
+    "rl_gru_categorical_workspace_bytes", "rl_gru_categorical_eval", "rl_gru_categorical_grad", "rl_gru_categorical_fvp",
+    "rl_rollout_population_gru", "rl_gae",
     "rl_discount_cumsum", "rl_debug_philox", "rl_policy_workspace_bytes", "rl_policy_activation_bytes", "rl_policy_loss_kl",
     "rl_policy_grad", "rl_policy_grad_loss", "rl_policy_fvp", "rl_policy_fvp_variant", "rl_policy_fvp_cg_step", "rl_cg_init", "rl_cg_step", "rl_trpo_step", "rl_line_search_point", "rl_line_search_decide", "rl_adam_step",
     "rl_path_scan", "rl_process_workspace_bytes", "rl_sample_stats_cols", "rl_sample_stats", "rl_adv_finish",
@@ -113,6 +115,19 @@ class GruBatch(ctypes.Structure):
         ("advantages", ctypes.c_void_p), ("old_means", ctypes.c_void_p), ("old_log_std", ctypes.c_void_p),
         ("start", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("means", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class GruCategoricalBatch(ctypes.Structure):
+    """Mirror of ``rl_gru_categorical_batch`` (include/rllab_amd.h): a recurrent categorical batch on its dense planes, the
+    one-hot planes as index planes, for the update kernels of a CategoricalGRUPolicy."""
+    _fields_ = [
+        ("n_envs", ctypes.c_int32), ("horizon", ctypes.c_int32), ("n_states", ctypes.c_int32), ("n_act", ctypes.c_int32),
+        ("hidden", ctypes.c_int32), ("include_action", ctypes.c_int32), ("inv_count", ctypes.c_double),
+        ("theta", ctypes.c_void_p), ("state", ctypes.c_void_p), ("action", ctypes.c_void_p),
+        ("advantages", ctypes.c_void_p), ("old_prob", ctypes.c_void_p), ("start", ctypes.c_void_p),
+        ("weights", ctypes.c_void_p), ("prob", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_size_t),
     ]
 
 
@@ -285,6 +300,11 @@ def _load():
     lib.rl_gru_gaussian_eval.argtypes = [ctypes.POINTER(GruBatch), vp, vp]
     lib.rl_gru_gaussian_grad.argtypes = [ctypes.POINTER(GruBatch), vp, vp, vp]
     lib.rl_gru_gaussian_fvp.argtypes = [ctypes.POINTER(GruBatch), vp, vp, vp]
+    lib.rl_gru_categorical_workspace_bytes.restype = ctypes.c_size_t
+    lib.rl_gru_categorical_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.rl_gru_categorical_eval.argtypes = [ctypes.POINTER(GruCategoricalBatch), vp, vp]
+    lib.rl_gru_categorical_grad.argtypes = [ctypes.POINTER(GruCategoricalBatch), vp, vp, vp]
+    lib.rl_gru_categorical_fvp.argtypes = [ctypes.POINTER(GruCategoricalBatch), vp, vp, vp]
     lib.rl_gae.argtypes = [i32, i32, vp, vp, vp, f64, f64, vp, vp, vp, vp]
     lib.rl_discount_cumsum.argtypes = [i32, i32, vp, vp, f64, vp, vp]
     lib.rl_debug_philox.argtypes = [u32, u32, u32, u32, u32, u32, i32, vp, vp]

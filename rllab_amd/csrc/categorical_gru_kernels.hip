@@ -6,7 +6,8 @@
 // state, so here they are evaluated per env and per step inside the launch: one env per lane, one wavefront per workgroup
 // of 64 envs, the GRU step, its parameter layout, the staged weights and the two hidden-state tiles of gru_cell.h.
 //
-// Local to this file: the horizon loop over the integer state machine of gridworld_lane.h, the softmax and the sampling.
+// Local to this file: the horizon loop over the integer state machine of gridworld_lane.h and the sampling (the softmax
+// is gridworld_lane.h's grid_softmax, which the update kernels of categorical_gru_bptt_kernels.hip evaluate too).
 // The input x = [onehot(s), onehot(prev_action)] is one-hot, so x W_x* is a ROW READ (OneHotInput): each gate's sum is its
 // bias, then row s of W_x*, then row S + prev_action of W_x* (skipped at a path start), then the hidden units in index
 // order with float32 FMAs -- six 16-byte reads at lane-varying addresses per unit block next to 3 H broadcast reads of W_h*.
@@ -53,13 +54,7 @@ __global__ void __launch_bounds__(GRU_BLOCK) gridworld_gru_rollout_kernel(rl_gri
         float logit[GRID_ACTIONS], p[GRID_ACTIONS];
         gru_cell<H, GRID_ACTIONS>(LdsWeights{lanes.w}, off, DI, OneHotInput<H>(S, s, include_action ? pa : -1), lanes.hc, lanes.hn, logit);
         lanes.swap();
-        // max-subtracted float32 softmax, the sum in index order
-        const float m = fmaxf(fmaxf(logit[0], logit[1]), fmaxf(logit[2], logit[3]));
-#pragma unroll
-        for (int k = 0; k < GRID_ACTIONS; ++k) p[k] = __builtin_amdgcn_exp2f((logit[k] - m) * 1.4426950408889634f);
-        const float iz = __builtin_amdgcn_rcpf(((p[0] + p[1]) + p[2]) + p[3]);
-#pragma unroll
-        for (int k = 0; k < GRID_ACTIONS; ++k) p[k] = p[k] * iz;
+        grid_softmax(logit, p);
         float u;
         if (a.u) u = a.u[col];
         else philox_draws<1, false>(&u, a.seed, env_global, a.step_counter + (uint64_t)t, RNG_POLICY);

@@ -21,6 +21,18 @@ __device__ __forceinline__ int grid_weighted_sample(const float* p, float u) {
     return act > GRID_ACTIONS - 1 ? GRID_ACTIONS - 1 : act;
 }
 
+// p = softmax(logit) of the four actions in float32: max-subtracted, exp2, the sum in index order, one rcp.  The recurrent
+// rollout records these probabilities and the recurrent update (categorical_gru_bptt_kernels.hip) evaluates them again:
+// one expression, so that at unchanged parameters the two agree bit for bit.
+__device__ __forceinline__ void grid_softmax(const float* logit, float* p) {
+    const float m = fmaxf(fmaxf(logit[0], logit[1]), fmaxf(logit[2], logit[3]));
+#pragma unroll
+    for (int k = 0; k < GRID_ACTIONS; ++k) p[k] = __builtin_amdgcn_exp2f((logit[k] - m) * 1.4426950408889634f);
+    const float iz = __builtin_amdgcn_rcpf(((p[0] + p[1]) + p[2]) + p[3]);
+#pragma unroll
+    for (int k = 0; k < GRID_ACTIONS; ++k) p[k] = p[k] * iz;
+}
+
 // get_possible_next_states / step: 0 left, 1 down, 2 right, 3 up; clipped at the border; a wall (or standing on a
 // hole / the goal) leaves the state where it is.  Returns the next state; `done` / `reward` are the env's own (a hole:
 // reward 0, done; the goal: reward 1, done) -- the horizon is the caller's.

@@ -12,7 +12,9 @@ stored [in, out] row-major, Glorot-uniform weights, zero biases and h0.  One ste
 ``prob = softmax(h' W_out + b_out)``.  ``prev_action`` is the SAMPLED action of the previous step of the same path and
 zeros at a path start; ``h`` is ``h0`` at a path start.  Sampling runs in the fused recurrent GridWorld rollout
 (csrc/categorical_gru_kernels.hip, ``rollout_layout``); the update runs through torch autograd on ``dist_info_planes``, a
-scan over the time axis of the dense [T, N] batch planes.
+scan over the time axis of the dense [T, N] batch planes -- or, with the engine option ``bptt_kernels=True`` and a
+ConjugateGradientOptimizer (TRPO, TNPG), on the back-propagation-through-time and Fisher-vector kernels of
+csrc/categorical_gru_bptt_kernels.hip (policies/fused_categorical_gru_ops.py).
 """
 import numpy as np
 import torch
@@ -30,8 +32,12 @@ LDS_BYTES = 160 * 1024            # of a CU: the kernel keeps the weights and tw
 
 class CategoricalGRUPolicy(GRUPolicyBase, StochasticPolicy, Serializable):
     def __init__(self, env_spec, hidden_dim=32, feature_network=None, state_include_action=True,
-                 hidden_nonlinearity=tanh):
+                 hidden_nonlinearity=tanh, **kwargs):
         Serializable.quick_init(self, locals())
+        # engine option, keyword only: loss, gradient and Fisher-vector products of a TRPO / TNPG update on HIP kernels
+        self.bptt_kernels = bool(kwargs.pop("bptt_kernels", False))
+        if kwargs:
+            raise TypeError("CategoricalGRUPolicy: unexpected arguments %r" % sorted(kwargs))
         assert isinstance(env_spec.action_space, Discrete)
         if feature_network is not None:
             raise NotImplementedError("CategoricalGRUPolicy(feature_network=...): the GRU reads the one-hot observation "
@@ -95,6 +101,36 @@ class CategoricalGRUPolicy(GRUPolicyBase, StochasticPolicy, Serializable):
         if self._state_include_action:
             agent_info["prev_action"] = prev_actions
         return actions, agent_info
+
+    # -- the update on the recurrent kernels --------------------------------------------------------------------------
+    def why_no_kernel_layout(self):
+        """Why the UPDATE of this policy runs through torch autograd (algos/npo.py::log_update_path), or None when
+        ``bptt_kernels=True`` and the kernels of csrc/categorical_gru_bptt_kernels.hip take it."""
+        if not self.bptt_kernels:
+            return GRUPolicyBase.why_no_kernel_layout(self)
+        if not 1 <= self.hidden_dim <= KERNEL_HIDDEN[-1]:
+            return "hidden_dim=%d: the recurrent update kernels run 1 .. %d hidden units" % (
+                self.hidden_dim, KERNEL_HIDDEN[-1])
+        if self.hidden_nonlinearity is not tanh:
+            return "hidden_nonlinearity is %s (the recurrent update kernels evaluate tanh)" % getattr(
+                self.hidden_nonlinearity, "__name__", repr(self.hidden_nonlinearity))
+        if self.action_dim != 4:
+            return "%d actions (the recurrent categorical update kernels are built for GridWorld's 4)" % self.action_dim
+        if not self.flat_params.is_cuda or self.flat_params.dtype != torch.float32:
+            return "the parameters are not float32 on a HIP device"
+        from rllab_amd import _lib
+        if _lib.lib.rl_gru_categorical_workspace_bytes(64, 1, self.obs_dim, self.kernel_hidden,
+                                                       int(self._state_include_action)) == 0:
+            return _lib.lib.rl_last_error().decode()
+        return None
+
+    def fused_ops(self):
+        """``FusedCategoricalGRUOps`` for a ConjugateGradientOptimizer, or None (then the update runs through torch
+        autograd and ``why_no_kernel_layout()`` says why)."""
+        if not self.bptt_kernels or self.why_no_kernel_layout() is not None:
+            return None
+        from rllab_amd.policies.fused_categorical_gru_ops import FusedCategoricalGRUOps
+        return FusedCategoricalGRUOps(self)
 
     # -- what the recurrent rollout kernel reads ----------------------------------------------------------------------
     def kernel_lds_bytes(self):

@@ -12,6 +12,9 @@ This is the subset of ``FusedGaussianMLPOps``' interface the optimizer calls whe
 it does here: ``h0`` is frozen, so the optimizer works in the trainable subspace.  The kernels run the policy at
 ``kernel_hidden`` units; ``scatter`` / ``gather`` move vectors between the flat order and that zero-padded layout
 (``GRUPolicyBase.pad_index``).
+
+``RecurrentOpsBase`` is everything here that does not name a distribution; ``FusedGRUOps`` adds the Gaussian descriptor and
+``policies/fused_categorical_gru_ops.py`` the categorical one.
 """
 import ctypes
 
@@ -23,8 +26,15 @@ from rllab_amd.misc import logger
 from rllab_amd.sampler import dist as D
 
 
-class FusedGRUOps(object):
+class RecurrentOpsBase(object):
+    """What the update passes of the two GRU policies share (``FusedGRUOps`` here, ``FusedCategoricalGRUOps`` in
+    policies/fused_categorical_gru_ops.py): the padded layout, the descriptor cache, the workspace, the loss record, and
+    the three passes as calls of the family's entry points.  A subclass names those (``ENTRY``), the field of its
+    descriptor that receives the forward sweep's head (``HEAD_FIELD``), and builds the descriptor of a tuple
+    (``_describe``) and ``accepts``."""
     device_line_search = False          # the host reads every line-search candidate, as the reference does
+    ENTRY = None                        # (eval, grad, fvp): names of the C entry points
+    HEAD_FIELD = None
 
     def __init__(self, policy):
         self.policy = policy
@@ -36,8 +46,6 @@ class FusedGRUOps(object):
             torch.as_tensor(idx, dtype=torch.long, device=dev)
         frozen = [np.arange(p.offset, p.offset + p.size) for p in policy.get_params() if not p.tags.get("trainable", False)]
         self.frozen = torch.as_tensor(np.concatenate(frozen), dtype=torch.long, device=dev) if frozen else None
-        self.dims = (int(policy.obs_dim), int(policy.action_dim), int(policy.kernel_hidden),
-                     int(policy.state_include_action))
         self._ws = None
         self._bound = {}
         self._loss_cache = None
@@ -58,19 +66,6 @@ class FusedGRUOps(object):
         return padded if self.index is None else padded.index_select(0, self.index.to(padded.device))
 
     # -- the batch ------------------------------------------------------------------------------------------------------
-    def accepts(self, inputs):
-        """(obs, actions, advantages, old mean, old log_std, start, weights, 1/W): [., T, N] planes on the device with ONE
-        old log_std row.  A tuple that is not one falls back to autograd inside the optimizer, behind init_opt's
-        ``update path: HIP kernels`` line: the log says so, once per tuple."""
-        ok = len(inputs) == 8 and inputs[0].is_cuda and inputs[0].dim() == 3 and inputs[0].shape[0] == self.dims[0] \
-            and inputs[4].numel() == self.dims[1] and not D.is_distributed()
-        key = id(inputs[0]) if len(inputs) else 0
-        if not ok and getattr(self, "_refused_key", None) != key:
-            self._refused_key = key
-            logger.log("update path: torch autograd for this batch -- its planes are not the [., T, N] device planes "
-                       "with one old log_std row that FusedGRUOps takes")
-        return ok
-
     def _eval_point(self, inputs):
         """(batch, parameter version)."""
         return (tuple(id(t) for t in inputs), self.policy.param_version())
@@ -81,29 +76,17 @@ class FusedGRUOps(object):
         key = tuple(id(t) for t in inputs)
         hit = self._bound.get(key)
         if hit is None:
-            obs, act, adv, old_mean, old_ls, start, w, inv_count = inputs
-            f32 = torch.float32
-            keep = [obs.to(f32).contiguous(), act.to(f32).contiguous(), adv.to(f32).contiguous(),
-                    old_mean.to(f32).contiguous(), old_ls.reshape(-1).to(f32).contiguous(),
-                    start.to(torch.uint8).contiguous(), w.to(f32).contiguous()]
-            do, da, H, inc = self.dims
-            T, N = int(obs.shape[1]), int(obs.shape[2])
-            need = _lib.lib.rl_gru_workspace_bytes(N, T, do, da, H, inc)
-            if need == 0:
-                raise RuntimeError("rl_gru_workspace_bytes: %s" % _lib.lib.rl_last_error().decode())
-            if self._ws is None or self._ws.numel() < need or self._ws.device != obs.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=obs.device)
+            dev = inputs[0].device
+            b, keep, need = self._describe(inputs)
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
                 self._state_tag = None
-            b = _lib.GruBatch(n_envs=N, horizon=T, obs_dim=do, act_dim=da, hidden=H, include_action=inc,
-                              inv_count=float(inv_count), obs=keep[0].data_ptr(), actions=keep[1].data_ptr(),
-                              advantages=keep[2].data_ptr(), old_means=keep[3].data_ptr(), old_log_std=keep[4].data_ptr(),
-                              start=keep[5].data_ptr(), weights=keep[6].data_ptr())
             self._bound.clear()              # one batch at a time: the workspace is one batch's
             hit = self._bound[key] = (b, keep + list(inputs))
         b = hit[0]
         b.theta = theta.data_ptr()
         b.workspace, b.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        b.means = None
+        setattr(b, self.HEAD_FIELD, None)
         self._theta_keep = theta
         return b
 
@@ -126,16 +109,20 @@ class FusedGRUOps(object):
             c["host"] = (float(h[0]), float(h[1]))
         return c["host"]
 
+    def _call(self, which, *args):
+        name = self.ENTRY[which]
+        _lib.check(getattr(_lib.lib, name)(*(args + (_lib.stream_ptr(),))), name)
+
     def _loss_eval(self, inputs, means=None):
+        """``means``: where the forward sweep leaves its head (the means; the probabilities), or None."""
         tag = self._eval_point(inputs)
         c = self._loss_cache
         if means is None and c is not None and c["tag"] == tag:
             return c
         b = self._batch(inputs)
-        b.means = None if means is None else means.data_ptr()
+        setattr(b, self.HEAD_FIELD, None if means is None else means.data_ptr())
         out2 = torch.empty(2, dtype=torch.float64, device=inputs[0].device)
-        _lib.check(_lib.lib.rl_gru_gaussian_eval(ctypes.byref(b), _lib.ptr(out2), _lib.stream_ptr()),
-                   "rl_gru_gaussian_eval")
+        self._call(0, ctypes.byref(b), _lib.ptr(out2))
         return self._record(tag, out2)
 
     def loss_and_kl(self, inputs):
@@ -147,27 +134,17 @@ class FusedGRUOps(object):
         c = self._loss_eval(inputs)
         return lambda: self._resolve(c)
 
-    def forward_means(self, inputs, with_grad=False):
-        """The means [Da, T, N] the forward sweep of the loss pass (``with_grad``: of the gradient pass) computes."""
-        means = torch.empty_like(inputs[3], dtype=torch.float32).contiguous()
-        if with_grad:
-            self.loss_grad(inputs, means=means)
-        else:
-            self._loss_eval(inputs, means=means)
-        return means
-
     # -- gradient and Fisher-vector product -----------------------------------------------------------------------------
     def loss_grad_kernel(self, inputs, with_loss=False, means=None):
         """The gradient of the surrogate loss in the kernel layout (float32, ``n_kernel`` entries)."""
         tag = self._eval_point(inputs)
         b = self._batch(inputs)
-        b.means = None if means is None else means.data_ptr()
+        setattr(b, self.HEAD_FIELD, None if means is None else means.data_ptr())
         dev = inputs[0].device
         out2 = torch.empty(2, dtype=torch.float64, device=dev)
         g = torch.empty(self.n_kernel, dtype=torch.float32, device=dev)
         self._state_tag = None
-        _lib.check(_lib.lib.rl_gru_gaussian_grad(ctypes.byref(b), _lib.ptr(out2), _lib.ptr(g), _lib.stream_ptr()),
-                   "rl_gru_gaussian_grad")
+        self._call(1, ctypes.byref(b), _lib.ptr(out2), _lib.ptr(g))
         self._state_tag = tag
         if with_loss and not (self._loss_cache is not None and self._loss_cache["tag"] == tag):
             self._record(tag, out2)
@@ -194,8 +171,7 @@ class FusedGRUOps(object):
         b = self._batch(inputs)
         out = torch.empty(self.n_kernel, dtype=torch.float32, device=inputs[0].device)
         v_kernel = v_kernel.contiguous()
-        _lib.check(_lib.lib.rl_gru_gaussian_fvp(ctypes.byref(b), _lib.ptr(v_kernel), _lib.ptr(out), _lib.stream_ptr()),
-                   "rl_gru_gaussian_fvp")
+        self._call(2, ctypes.byref(b), _lib.ptr(v_kernel), _lib.ptr(out))
         return out
 
     def fvp(self, inputs, full):
@@ -206,3 +182,53 @@ class FusedGRUOps(object):
     def hvp_approach(self):
         from rllab_amd.policies.fused_ops import FusedFisherHvp
         return FusedFisherHvp(self)
+
+
+class FusedGRUOps(RecurrentOpsBase):
+    ENTRY = ("rl_gru_gaussian_eval", "rl_gru_gaussian_grad", "rl_gru_gaussian_fvp")
+    HEAD_FIELD = "means"
+
+    def __init__(self, policy):
+        RecurrentOpsBase.__init__(self, policy)
+        self.dims = (int(policy.obs_dim), int(policy.action_dim), int(policy.kernel_hidden),
+                     int(policy.state_include_action))
+
+    def accepts(self, inputs):
+        """(obs, actions, advantages, old mean, old log_std, start, weights, 1/W): [., T, N] planes on the device with ONE
+        old log_std row.  A tuple that is not one falls back to autograd inside the optimizer, behind init_opt's
+        ``update path: HIP kernels`` line: the log says so, once per tuple."""
+        ok = len(inputs) == 8 and inputs[0].is_cuda and inputs[0].dim() == 3 and inputs[0].shape[0] == self.dims[0] \
+            and inputs[4].numel() == self.dims[1] and not D.is_distributed()
+        key = id(inputs[0]) if len(inputs) else 0
+        if not ok and getattr(self, "_refused_key", None) != key:
+            self._refused_key = key
+            logger.log("update path: torch autograd for this batch -- its planes are not the [., T, N] device planes "
+                       "with one old log_std row that FusedGRUOps takes")
+        return ok
+
+    def _describe(self, inputs):
+        """(descriptor, the tensors it points into, workspace bytes) of an input tuple."""
+        obs, act, adv, old_mean, old_ls, start, w, inv_count = inputs
+        f32 = torch.float32
+        keep = [obs.to(f32).contiguous(), act.to(f32).contiguous(), adv.to(f32).contiguous(),
+                old_mean.to(f32).contiguous(), old_ls.reshape(-1).to(f32).contiguous(),
+                start.to(torch.uint8).contiguous(), w.to(f32).contiguous()]
+        do, da, H, inc = self.dims
+        T, N = int(obs.shape[1]), int(obs.shape[2])
+        need = _lib.lib.rl_gru_workspace_bytes(N, T, do, da, H, inc)
+        if need == 0:
+            raise RuntimeError("rl_gru_workspace_bytes: %s" % _lib.lib.rl_last_error().decode())
+        b = _lib.GruBatch(n_envs=N, horizon=T, obs_dim=do, act_dim=da, hidden=H, include_action=inc,
+                          inv_count=float(inv_count), obs=keep[0].data_ptr(), actions=keep[1].data_ptr(),
+                          advantages=keep[2].data_ptr(), old_means=keep[3].data_ptr(), old_log_std=keep[4].data_ptr(),
+                          start=keep[5].data_ptr(), weights=keep[6].data_ptr())
+        return b, keep, need
+
+    def forward_means(self, inputs, with_grad=False):
+        """The means [Da, T, N] the forward sweep of the loss pass (``with_grad``: of the gradient pass) computes."""
+        means = torch.empty_like(inputs[3], dtype=torch.float32).contiguous()
+        if with_grad:
+            self.loss_grad(inputs, means=means)
+        else:
+            self._loss_eval(inputs, means=means)
+        return means
