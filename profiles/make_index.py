@@ -18,6 +18,8 @@ RECIPES = [
      "python tools/exp/gru_bptt_time.py --out profiles/gru_bptt_time.json"),
     ("categorical_gru_bptt_time.json", "loss + KL, gradient and Fisher-vector product of a CategoricalGRUPolicy per call, and one whole TRPO update: the recurrent categorical update kernels next to the float32 autograd closures, the sampler's batch for 4096 GridWorld 4x4 envs, max_path_length 100, 32 units",
      "python tools/exp/categorical_gru_bptt_time.py --out profiles/categorical_gru_bptt_time.json"),
+    ("update_batch_refactor_time.json", "parent commit against the update-batch / planes-ops refactor on one box, runs interleaved: headline bench (env steps/s, update phase) and whole TRPO iterations of GaussianMLPPolicy(adaptive_std=True) on Cartpole (1024 x 100) and CategoricalMLPPolicy on GridWorld (80 x 50); every run, medians, the parent's own spread",
+     "python tools/exp/update_batch_refactor_ab.py --parent <built checkout of the parent> --out profiles/update_batch_refactor_time.json"),
     ("*_bench_line.json", "the default bench line of that tree", "python bench.py"),
     ("*_bench_under_rocprof.log", "bench stdout under the kernel-trace pass", "profiles/run_profile.sh <tag>"),
     ("*_c5_kernel_stats.csv", "kernel stats of C5's per-GPU shard", "profiles/run_profile.sh <tag> cheetah1024_trpo_gae"),

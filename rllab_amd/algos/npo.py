@@ -5,10 +5,8 @@
     mean_kl(theta)   =   sum_b w_b * KL(old_b || theta) / W
 (reference :72-82; w = 0/1 validity weights of the dense batch, W = global number
 of valid samples, so a sum all-reduce over env shards yields the global mean).
-Inputs follow the reference's order [obs, actions, advantages, *state_infos,
-old mean, old log_std] (:84-88) with the two batch-normalisation extras appended:
-[..., weights, 1/W].  All per-sample tensors are "planes" with the sample axis
-LAST (obs [Do, B], actions [Da, B], ...).
+The inputs are the policy's update batch (rllab_amd/policies/update_batch.py: the four signatures and their order).  All
+per-sample tensors are "planes" with the sample axis LAST (obs [Do, B], actions [Da, B], ...).
 """
 import os
 
@@ -16,40 +14,36 @@ import torch
 
 import rllab_amd.misc.logger as logger
 from rllab_amd.algos.batch_polopt import BatchPolopt
+from rllab_amd.policies.update_batch import is_categorical, new_dist, old_dist, signature_of
 from rllab_amd.sampler import dist as D
 
 
 def npo_inputs(policy, samples_data):
-    """Build the optimizer input tuple from a processed dense batch."""
+    """Build the optimizer input tuple (the policy's signature of policies/update_batch.py) from a processed dense batch."""
     traj = samples_data["_traj"]
     B = traj.B
-    w = traj.valid.reshape(B).to(torch.float32)
+    sig = signature_of(policy)
     if getattr(traj, "count", None) is not None:
         # process_samples already read the global number of valid samples (rl_sample_stats): no second
         # reduction + blocking read for 1 / W
         cnt = torch.tensor(float(traj.count), dtype=torch.float64)
     else:
-        cnt = D.all_reduce_sum_(w.to(torch.float64).sum())
-    if getattr(traj, "categorical", False) and getattr(policy, "recurrent", False):
-        # a recurrent categorical policy: the one-hot planes stay [., T, N] and the path starts ride along:
-        # (obs, actions, advantages, old_prob, start, weights, 1/W)
-        return (traj.obs, traj.actions, traj.advantages, traj.means, (traj.tin == 0), traj.valid.to(torch.float32),
-                (1.0 / cnt))
-    if getattr(traj, "categorical", False):
-        # a categorical policy: (obs, actions, advantages, old_prob, weights, 1/W) -- one-hot planes, recorded probabilities
-        return (traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B), traj.advantages.reshape(B),
-                traj.means.reshape(traj.act_dim, B), w, (1.0 / cnt))
-    if getattr(policy, "recurrent", False):
+        cnt = D.all_reduce_sum_(traj.valid.reshape(B).to(torch.float64).sum())
+    if sig.has_start:
         # a recurrent policy: the planes stay [., T, N] -- its forward pass is a scan over t of every env column -- and the
-        # path starts ride along: (obs, actions, advantages, old mean, old log_std, start, weights, 1/W)
-        if traj.log_std_planes is not None:
-            raise NotImplementedError("a recurrent batch with per-sample log_std planes")
-        return (traj.obs, traj.actions, traj.advantages, traj.means, traj.log_std.reshape(-1, 1, 1),
-                (traj.tin == 0), traj.valid.to(torch.float32), (1.0 / cnt))
-    old_ls = traj.log_std.reshape(-1, 1) if traj.log_std_planes is None \
-        else traj.log_std_planes.reshape(traj.act_dim, B)
-    return (traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B),
-            traj.advantages.reshape(B), traj.means.reshape(traj.act_dim, B), old_ls, w, (1.0 / cnt))
+        # path starts ride along
+        old = (traj.means,)
+        if "old_log_std" in sig._fields:
+            if traj.log_std_planes is not None:
+                raise NotImplementedError("a recurrent batch with per-sample log_std planes")
+            old += (traj.log_std.reshape(-1, 1, 1),)
+        return sig(traj.obs, traj.actions, traj.advantages, *old, (traj.tin == 0), traj.valid.to(torch.float32), (1.0 / cnt))
+    # the MLP families: flat [., B] planes (a categorical batch: one-hot planes, the recorded probabilities as ``means``)
+    old = (traj.means.reshape(traj.act_dim, B),)
+    if "old_log_std" in sig._fields:
+        old += (traj.log_std.reshape(-1, 1) if traj.log_std_planes is None else traj.log_std_planes.reshape(traj.act_dim, B),)
+    return sig(traj.obs.reshape(traj.obs_dim, B), traj.actions.reshape(traj.act_dim, B), traj.advantages.reshape(B), *old,
+               traj.valid.reshape(B).to(torch.float32), (1.0 / cnt))
 
 
 def log_update_path(policy, fused, why=None):
@@ -64,11 +58,6 @@ def log_update_path(policy, fused, why=None):
         # nothing about the policy keeps it off its kernels: the caller is not the optimizer they are built for
         why = "the recurrent kernels serve ConjugateGradientOptimizer (TRPO, TNPG)"
     logger.log("update path: torch autograd%s" % ("" if why is None else " -- " + why))
-
-
-def is_categorical(policy):
-    """A policy over discrete actions (CategoricalMLPPolicy): its distribution's parameters are the probabilities."""
-    return list(getattr(policy.distribution, "dist_info_keys", [])) == ["prob"]
 
 
 def check_categorical_supported(policy):
@@ -112,82 +101,42 @@ class NPO(BatchPolopt):
         policy = self.policy
         dist = policy.distribution
         trunc = self.truncate_local_is_ratio
-
-        def _new_dist(flat, obs):
-            return policy.dist_info_planes(obs, flat)
-
-        def surr_loss(flat, obs, act, adv, old_mean, old_log_std, w, inv_count):
-            new = _new_dist(flat, obs)
-            old = dict(mean=old_mean, log_std=old_log_std)
-            lr = dist.likelihood_ratio_sym(act, old, new, axis=0)
-            if trunc is not None:
-                lr = torch.clamp(lr, max=trunc)
-            return -(lr * adv * w).sum() * inv_count.to(lr.dtype)
-
-        def mean_kl(flat, obs, act, adv, old_mean, old_log_std, w, inv_count):
-            new = _new_dist(flat, obs)
-            old = dict(mean=old_mean, log_std=old_log_std)
-            kl = dist.kl_sym(old, new, axis=0)
-            return (kl * w).sum() * inv_count.to(kl.dtype)
-
+        sig = signature_of(policy)
         if policy.recurrent:
             check_recurrent_supported(policy, self.optimizer)
-
-            # the reference's masked means over [paths, max_path_length] (npo.py:72-79 with ``valids``) on the dense planes
-            def surr_loss(flat, obs, act, adv, old_mean, old_log_std, start, w, inv_count):  # noqa: F811
-                new = policy.dist_info_planes(obs, act, start, flat)
-                lr = dist.likelihood_ratio_sym(act, dict(mean=old_mean, log_std=old_log_std), new, axis=0)
-                if trunc is not None:
-                    lr = torch.clamp(lr, max=trunc)
-                return -(lr * adv * w).sum() * inv_count.to(lr.dtype)
-
-            def mean_kl(flat, obs, act, adv, old_mean, old_log_std, start, w, inv_count):  # noqa: F811
-                new = policy.dist_info_planes(obs, act, start, flat)
-                kl = dist.kl_sym(dict(mean=old_mean, log_std=old_log_std), new, axis=0)
-                return (kl * w).sum() * inv_count.to(kl.dtype)
-
         if is_categorical(policy):
             check_categorical_supported(policy)
 
-            def surr_loss(flat, obs, act, adv, old_prob, w, inv_count):  # noqa: F811
-                lr = dist.likelihood_ratio_sym(act, dict(prob=old_prob), _new_dist(flat, obs), axis=0)
-                if trunc is not None:
-                    lr = torch.clamp(lr, max=trunc)
-                return -(lr * adv * w).sum() * inv_count.to(lr.dtype)
+        # (recurrent: the reference's masked means over [paths, max_path_length], npo.py:72-79 with ``valids``, on the dense
+        # planes)
+        def surr_loss(flat, *inputs):
+            b = sig._make(inputs)
+            lr = dist.likelihood_ratio_sym(b.actions, old_dist(b), new_dist(policy, b, flat), axis=0)
+            if trunc is not None:
+                lr = torch.clamp(lr, max=trunc)
+            return -(lr * b.advantages * b.weights).sum() * b.inv_count.to(lr.dtype)
 
-            def mean_kl(flat, obs, act, adv, old_prob, w, inv_count):  # noqa: F811
-                kl = dist.kl_sym(dict(prob=old_prob), _new_dist(flat, obs), axis=0)
-                return (kl * w).sum() * inv_count.to(kl.dtype)
-
-        if policy.recurrent and is_categorical(policy):
-            # both of the above apply (one GPU, whole paths); the closures are the recurrent ones on the "prob" planes
-            def surr_loss(flat, obs, act, adv, old_prob, start, w, inv_count):  # noqa: F811
-                new = policy.dist_info_planes(obs, act, start, flat)
-                lr = dist.likelihood_ratio_sym(act, dict(prob=old_prob), new, axis=0)
-                if trunc is not None:
-                    lr = torch.clamp(lr, max=trunc)
-                return -(lr * adv * w).sum() * inv_count.to(lr.dtype)
-
-            def mean_kl(flat, obs, act, adv, old_prob, start, w, inv_count):  # noqa: F811
-                kl = dist.kl_sym(dict(prob=old_prob), policy.dist_info_planes(obs, act, start, flat), axis=0)
-                return (kl * w).sum() * inv_count.to(kl.dtype)
+        def mean_kl(flat, *inputs):
+            b = sig._make(inputs)
+            kl = dist.kl_sym(old_dist(b), new_dist(policy, b, flat), axis=0)
+            return (kl * b.weights).sum() * b.inv_count.to(kl.dtype)
 
         fused = None
+        trunc_why = None if trunc is None else \
+            "truncate_local_is_ratio is set (the kernels evaluate the plain likelihood ratio)"
         if policy.recurrent:
             # GaussianGRUPolicy(bptt_kernels=True) under a ConjugateGradientOptimizer: policies/fused_gru_ops.py
             from rllab_amd.optimizers.conjugate_gradient_optimizer import ConjugateGradientOptimizer
             why = None
             if getattr(policy, "bptt_kernels", False) and hasattr(policy, "fused_ops"):
-                if trunc is not None:
-                    why = "truncate_local_is_ratio is set (the kernels evaluate the plain likelihood ratio)"
-                elif isinstance(self.optimizer, ConjugateGradientOptimizer) and getattr(self, "use_fused", True):
+                why = trunc_why
+                if trunc is None and isinstance(self.optimizer, ConjugateGradientOptimizer) and getattr(self, "use_fused", True):
                     fused = policy.fused_ops()
             log_update_path(policy, fused, why)
-        elif trunc is None and hasattr(policy, "fused_ops") and getattr(self, "use_fused", True):
-            fused = policy.fused_ops()
-        if not policy.recurrent:
-            log_update_path(policy, fused, "truncate_local_is_ratio is set (the kernels evaluate the plain likelihood "
-                                           "ratio)" if trunc is not None else None)
+        else:
+            if trunc is None and hasattr(policy, "fused_ops") and getattr(self, "use_fused", True):
+                fused = policy.fused_ops()
+            log_update_path(policy, fused, trunc_why)
         self.optimizer.update_opt(loss=surr_loss, target=policy, leq_constraint=(mean_kl, self.step_size),
                                   inputs=None, constraint_name="mean_kl", fused=fused)
         return dict()

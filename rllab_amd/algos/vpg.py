@@ -8,10 +8,10 @@ import torch
 
 import rllab_amd.misc.logger as logger
 from rllab_amd.algos.batch_polopt import BatchPolopt
-from rllab_amd.algos.npo import (check_categorical_supported, check_recurrent_supported, is_categorical, log_update_path,
-                                 npo_inputs)
+from rllab_amd.algos.npo import check_categorical_supported, check_recurrent_supported, log_update_path, npo_inputs
 from rllab_amd.core.serializable import Serializable
 from rllab_amd.optimizers.first_order_optimizer import FirstOrderOptimizer
+from rllab_amd.policies.update_batch import is_categorical, new_dist, old_dist, signature_of
 from rllab_amd.sampler import dist as D
 
 
@@ -29,80 +29,40 @@ class VPG(BatchPolopt, Serializable):
     def init_opt(self):
         policy = self.policy
         dist = policy.distribution
-
-        def surr_obj(flat, obs, act, adv, old_mean, old_log_std, w, inv_count):
-            new = policy.dist_info_planes(obs, flat)
-            logli = dist.log_likelihood_sym(act, new, axis=0)
-            return -(logli * adv * w).sum() * inv_count.to(logli.dtype)
-
-        def f_kl(inputs):
-            obs, act, adv, old_mean, old_log_std, w, inv_count = inputs
-            with torch.no_grad():
-                new = policy.dist_info_planes(obs)
-                kl = dist.kl_sym(dict(mean=old_mean, log_std=old_log_std), new, axis=0)
-                mean_kl = D.all_reduce_sum_(((kl * w).sum() * inv_count.to(kl.dtype)).to(torch.float64))
-                neg = torch.full_like(kl, -float("inf"))
-                max_kl = D.all_reduce_max_(torch.where(w > 0, kl, neg).max().to(torch.float64))
-            return float(mean_kl), float(max_kl)
-
+        sig = signature_of(policy)
         if policy.recurrent:
             check_recurrent_supported(policy, self.optimizer)
-
-            # the reference's masked means (vpg.py:60-75 with ``valids``) on the dense [., T, N] planes
-            def surr_obj(flat, obs, act, adv, old_mean, old_log_std, start, w, inv_count):  # noqa: F811
-                logli = dist.log_likelihood_sym(act, policy.dist_info_planes(obs, act, start, flat), axis=0)
-                return -(logli * adv * w).sum() * inv_count.to(logli.dtype)
-
-            def f_kl(inputs):  # noqa: F811
-                obs, act, adv, old_mean, old_log_std, start, w, inv_count = inputs
-                with torch.no_grad():
-                    kl = dist.kl_sym(dict(mean=old_mean, log_std=old_log_std), policy.dist_info_planes(obs, act, start),
-                                     axis=0)
-                    mean_kl = ((kl * w).sum() * inv_count.to(kl.dtype)).to(torch.float64)
-                    max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
-                return float(mean_kl), float(max_kl)
-
         if is_categorical(policy):
             check_categorical_supported(policy)
 
-            def surr_obj(flat, obs, act, adv, old_prob, w, inv_count):  # noqa: F811
-                logli = dist.log_likelihood_sym(act, policy.dist_info_planes(obs, flat), axis=0)
-                return -(logli * adv * w).sum() * inv_count.to(logli.dtype)
+        # (recurrent: the reference's masked means, vpg.py:60-75 with ``valids``, on the dense [., T, N] planes)
+        def surr_obj(flat, *inputs):
+            b = sig._make(inputs)
+            logli = dist.log_likelihood_sym(b.actions, new_dist(policy, b, flat), axis=0)
+            return -(logli * b.advantages * b.weights).sum() * b.inv_count.to(logli.dtype)
 
-            def f_kl(inputs):  # noqa: F811
-                obs, act, adv, old_prob, w, inv_count = inputs
-                with torch.no_grad():
-                    kl = dist.kl_sym(dict(prob=old_prob), policy.dist_info_planes(obs), axis=0)
-                    mean_kl = ((kl * w).sum() * inv_count.to(kl.dtype)).to(torch.float64)
-                    max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
-                return float(mean_kl), float(max_kl)
-
-        if policy.recurrent and is_categorical(policy):
-            # both of the above apply (one GPU, whole paths); the closures are the recurrent ones on the "prob" planes
-            def surr_obj(flat, obs, act, adv, old_prob, start, w, inv_count):  # noqa: F811
-                logli = dist.log_likelihood_sym(act, policy.dist_info_planes(obs, act, start, flat), axis=0)
-                return -(logli * adv * w).sum() * inv_count.to(logli.dtype)
-
-            def f_kl(inputs):  # noqa: F811
-                obs, act, adv, old_prob, start, w, inv_count = inputs
-                with torch.no_grad():
-                    kl = dist.kl_sym(dict(prob=old_prob), policy.dist_info_planes(obs, act, start), axis=0)
-                    mean_kl = ((kl * w).sum() * inv_count.to(kl.dtype)).to(torch.float64)
-                    max_kl = torch.where(w > 0, kl, torch.full_like(kl, -float("inf"))).max().to(torch.float64)
-                return float(mean_kl), float(max_kl)
+        def f_kl(inputs):
+            b = sig._make(inputs)
+            with torch.no_grad():
+                kl = dist.kl_sym(old_dist(b), new_dist(policy, b), axis=0)
+                # (the all-reduces are the identity in one process; only the Gaussian MLP family runs sharded)
+                mean_kl = D.all_reduce_sum_(((kl * b.weights).sum() * b.inv_count.to(kl.dtype)).to(torch.float64))
+                neg = torch.full_like(kl, -float("inf"))
+                max_kl = D.all_reduce_max_(torch.where(b.weights > 0, kl, neg).max().to(torch.float64))
+            return float(mean_kl), float(max_kl)
 
         fused = policy.fused_ops() if hasattr(policy, "fused_ops") and getattr(self, "use_fused", True) \
             and not policy.recurrent else None
         log_update_path(policy, fused)
-        if fused is not None:
-            def f_kl(inputs):  # noqa: F811  (HIP kernel version of the same statistic)
-                s = fused.loss_stats_host(inputs)      # the evaluation's one host read (shared with loss())
-                return s[1], s[3]
+
+        def fused_f_kl(inputs):                        # (HIP kernel version of the same statistic)
+            s = fused.loss_stats_host(inputs)          # the evaluation's one host read (shared with loss())
+            return s[1], s[3]
         # fused_loglik: surr_obj is the log-likelihood objective, not NPO's likelihood-ratio surrogate (LbfgsOptimizer asks
         # the fused object for the matching value / gradient: ERWR; the other optimizers ignore the keyword)
         self.optimizer.update_opt(surr_obj, target=policy, inputs=None, fused=fused, weighted_mean_inputs=True,
                                   fused_loglik=True)
-        self.opt_info = dict(f_kl=f_kl)
+        self.opt_info = dict(f_kl=f_kl if fused is None else fused_f_kl)
 
     def optimize_policy(self, itr, samples_data):
         logger.log("optimizing policy")

@@ -249,7 +249,7 @@ class ConjugateGradientOptimizer(Serializable):
             subsample_inputs = list(
                 x.index_select(-1, inds) if torch.is_tensor(x) and x.dim() > 0 and x.shape[-1] == n_samples
                 else x for x in inputs)
-            # input convention (algos/npo.py): [..., weights, inv_count]; renormalise the mean
+            # every update batch (policies/update_batch.py) ends [..., weights, inv_count]: renormalise the mean
             cnt = D.all_reduce_sum_(subsample_inputs[-2].to(torch.float64).sum())
             subsample_inputs[-1] = (1.0 / cnt).to(inputs[-1].dtype)
             subsample_inputs = tuple(subsample_inputs)

@@ -110,13 +110,13 @@ class CategoricalMLPPolicy(StochasticPolicy, Serializable):
         """One sentence naming what keeps this policy's update off the HIP kernels, or None."""
         if self.num_seq_inputs != 1:
             return "num_seq_inputs = %d: the kernels take one observation per sample" % self.num_seq_inputs
-        from rllab_amd.policies.fused_categorical_ops import KernelNet
+        from rllab_amd.policies.planes_ops import KernelNet
         return KernelNet.why_not(self, self._logit_network)
 
     def kernel_net(self):
-        """The kernels' copy of the logit network (policies/fused_categorical_ops.py::KernelNet), or None."""
+        """The kernels' copy of the logit network (policies/planes_ops.py::KernelNet), or None."""
         if not hasattr(self, "_kernel_net"):
-            from rllab_amd.policies.fused_categorical_ops import KernelNet
+            from rllab_amd.policies.planes_ops import KernelNet
             self._kernel_net = KernelNet(self, self._logit_network) if self.why_no_kernel_layout() is None else None
         return self._kernel_net
 

@@ -1,8 +1,7 @@
 """HIP-kernel loss / gradient / Fisher-vector product of a GaussianGRUPolicy for ConjugateGradientOptimizer (TRPO, TNPG).
 
-The three passes of csrc/gru_bptt_kernels.hip on the dense planes of a recurrent batch, the tuple
-``rllab_amd.algos.npo.npo_inputs`` builds: (obs [Do,T,N], actions [Da,T,N], advantages [T,N], old mean [Da,T,N],
-old log_std [Da], start [T,N], weights [T,N], 1/W).
+The three passes of csrc/gru_bptt_kernels.hip on the dense [., T, N] planes of a recurrent Gaussian update batch
+(policies/update_batch.py; one old log_std row [Da]).
 
     loss, KL   : rl_gru_gaussian_eval   one forward sweep (every line-search candidate)
     gradient   : rl_gru_gaussian_grad   forward sweep, backward sweep, the weight sums on the matrix cores; also loss, KL
@@ -23,6 +22,7 @@ import torch
 
 from rllab_amd import _lib
 from rllab_amd.misc import logger
+from rllab_amd.policies.update_batch import RecurrentGaussianBatch as Batch
 from rllab_amd.sampler import dist as D
 
 
@@ -194,11 +194,12 @@ class FusedGRUOps(RecurrentOpsBase):
                      int(policy.state_include_action))
 
     def accepts(self, inputs):
-        """(obs, actions, advantages, old mean, old log_std, start, weights, 1/W): [., T, N] planes on the device with ONE
-        old log_std row.  A tuple that is not one falls back to autograd inside the optimizer, behind init_opt's
-        ``update path: HIP kernels`` line: the log says so, once per tuple."""
-        ok = len(inputs) == 8 and inputs[0].is_cuda and inputs[0].dim() == 3 and inputs[0].shape[0] == self.dims[0] \
-            and inputs[4].numel() == self.dims[1] and not D.is_distributed()
+        """A recurrent Gaussian batch of [., T, N] planes on the device with ONE old log_std row.  A tuple that is not one
+        falls back to autograd inside the optimizer, behind init_opt's ``update path: HIP kernels`` line: the log says so,
+        once per tuple."""
+        b = Batch._make(inputs) if len(inputs) == len(Batch._fields) else None
+        ok = b is not None and b.obs.is_cuda and b.obs.dim() == 3 and b.obs.shape[0] == self.dims[0] \
+            and b.old_log_std.numel() == self.dims[1] and not D.is_distributed()
         key = id(inputs[0]) if len(inputs) else 0
         if not ok and getattr(self, "_refused_key", None) != key:
             self._refused_key = key
@@ -208,25 +209,25 @@ class FusedGRUOps(RecurrentOpsBase):
 
     def _describe(self, inputs):
         """(descriptor, the tensors it points into, workspace bytes) of an input tuple."""
-        obs, act, adv, old_mean, old_ls, start, w, inv_count = inputs
+        named = Batch._make(inputs)
         f32 = torch.float32
-        keep = [obs.to(f32).contiguous(), act.to(f32).contiguous(), adv.to(f32).contiguous(),
-                old_mean.to(f32).contiguous(), old_ls.reshape(-1).to(f32).contiguous(),
-                start.to(torch.uint8).contiguous(), w.to(f32).contiguous()]
+        keep = [named.obs.to(f32).contiguous(), named.actions.to(f32).contiguous(), named.advantages.to(f32).contiguous(),
+                named.old_mean.to(f32).contiguous(), named.old_log_std.reshape(-1).to(f32).contiguous(),
+                named.start.to(torch.uint8).contiguous(), named.weights.to(f32).contiguous()]
         do, da, H, inc = self.dims
-        T, N = int(obs.shape[1]), int(obs.shape[2])
+        T, N = int(named.obs.shape[1]), int(named.obs.shape[2])
         need = _lib.lib.rl_gru_workspace_bytes(N, T, do, da, H, inc)
         if need == 0:
             raise RuntimeError("rl_gru_workspace_bytes: %s" % _lib.lib.rl_last_error().decode())
         b = _lib.GruBatch(n_envs=N, horizon=T, obs_dim=do, act_dim=da, hidden=H, include_action=inc,
-                          inv_count=float(inv_count), obs=keep[0].data_ptr(), actions=keep[1].data_ptr(),
+                          inv_count=float(named.inv_count), obs=keep[0].data_ptr(), actions=keep[1].data_ptr(),
                           advantages=keep[2].data_ptr(), old_means=keep[3].data_ptr(), old_log_std=keep[4].data_ptr(),
                           start=keep[5].data_ptr(), weights=keep[6].data_ptr())
         return b, keep, need
 
     def forward_means(self, inputs, with_grad=False):
         """The means [Da, T, N] the forward sweep of the loss pass (``with_grad``: of the gradient pass) computes."""
-        means = torch.empty_like(inputs[3], dtype=torch.float32).contiguous()
+        means = torch.empty_like(Batch._make(inputs).old_mean, dtype=torch.float32).contiguous()
         if with_grad:
             self.loss_grad(inputs, means=means)
         else:

@@ -2,7 +2,8 @@
 (csrc/policy_kernels.hip through the C ABI): surrogate loss + mean KL, flat
 gradient, Fisher-vector product.  Each result is a SUM of per-rank terms already
 normalised by the global sample count, all-reduced here (RCCL) so callers see
-global values.  Inputs are the tuples built by ``rllab_amd.algos.npo.npo_inputs``.
+global values.  Inputs are Gaussian update batches (policies/update_batch.py), as ``rllab_amd.algos.npo.npo_inputs``
+builds them.
 """
 import ctypes
 import math
@@ -13,6 +14,7 @@ import torch
 from rllab_amd import _lib
 from rllab_amd.core.serializable import Serializable
 from rllab_amd.misc.device_io import read_async
+from rllab_amd.policies.update_batch import GaussianBatch
 from rllab_amd.sampler import dist as D
 
 
@@ -20,16 +22,20 @@ class FusedGaussianMLPOps(object):
     device_line_search = True    # line_search_device / line_search_resolve are available (ConjugateGradientOptimizer asks)
 
     def __init__(self, policy):
-        self.policy = policy
-        self.layout = policy.kernel_layout()
-        assert self.layout is not None
+        layout = policy.kernel_layout()
+        assert layout is not None
         # what the kernels are told: the padded hidden widths (policies/kernel_layout.py); P_pad parameters
-        self.dims = (policy.obs_dim, policy.action_dim) + self.layout.hidden3
-        self.n_kernel = self.layout.P_pad
+        self._bind(policy, layout, (policy.obs_dim, policy.action_dim) + layout.hidden3)
         # which kernel family the library picks for these dimensions (csrc/policy_kernels.hip::dispatch_net): the
         # cooperative kernels for wide / deep nets AND for equal-width nets on (obs_dim, action_dim) pairs the
         # one-wavefront-per-tile kernels are not instantiated for (they take the dimensions at run time)
-        self.wide_kernels = self.layout.wide or (policy.obs_dim, policy.action_dim) not in self.NARROW_PAIRS
+        self.wide_kernels = layout.wide or (policy.obs_dim, policy.action_dim) not in self.NARROW_PAIRS
+
+    def _bind(self, policy, layout, dims):
+        """The state every ops class of this family starts from: whose parameters, in which layout the optimizer sees them,
+        the dimensions the kernels are told, and the empty per-batch caches."""
+        self.policy, self.layout, self.dims = policy, layout, dims
+        self.n_kernel = layout.P_pad
         self._ws = None
         self._loss_cache = None
         self._bound = {}     # key -> (PolicyBatch, tensors kept alive, inv_count float); <= 2 entries
@@ -61,7 +67,10 @@ class FusedGaussianMLPOps(object):
 
     def accepts(self, inputs):
         """The kernels take ONE old log_std row (state-independent std)."""
-        return inputs[4].numel() == self.dims[1] and inputs[0].is_cuda
+        if len(inputs) != len(GaussianBatch._fields):
+            return False
+        b = GaussianBatch._make(inputs)
+        return b.old_log_std.numel() == self.dims[1] and b.obs.is_cuda
 
     def _workspace(self, device):
         if self._ws is None or self._ws.device != device:
@@ -78,13 +87,14 @@ class FusedGaussianMLPOps(object):
         hit = self._bound.get(key)
         if hit is not None:
             return hit
-        obs, act, adv, old_mean, old_log_std, w, inv_count = inputs
+        named = GaussianBatch._make(inputs)
         theta = self.layout.theta()          # kernel layout; a persistent buffer, refreshed in place (_refresh)
-        keep = [t.contiguous() for t in (obs, act, adv, old_mean, old_log_std.reshape(-1).float(), w, theta)]
+        keep = [t.contiguous() for t in (named.obs, named.actions, named.advantages, named.old_mean,
+                                         named.old_log_std.reshape(-1).float(), named.weights, theta)]
         obs, act, adv, old_mean, old_ls, w, theta = keep
         assert theta.data_ptr() == self.layout.theta().data_ptr()       # updates are in place
         pol = self.policy
-        inv = float(inv_count)
+        inv = float(named.inv_count)
         b = _lib.PolicyBatch(
             n_samples=obs.shape[-1], obs_dim=self.dims[0], act_dim=self.dims[1], hidden0=self.dims[2],
             hidden1=self.dims[3], hidden2=self.dims[4], inv_count=inv,
