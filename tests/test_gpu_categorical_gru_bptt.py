@@ -45,10 +45,11 @@ def _policy(desc, hidden, seed=0, scale=0.1, **kw):
     return env, pol
 
 
-def _planes(pol, N, T, seed=3, at_old=False):
+def _planes(pol, N, T, seed=3, at_old=False, edit=None):
     """Synthetic planes in the order of npo_inputs: random state and action indices as one-hot planes.  ``at_old``:
     old == new (the point the Fisher matrix is taken at); else the old probabilities are the softmax of the current logits
-    plus 0.3 randn: lr != 1, the KL of order 1e-2."""
+    plus 0.3 randn: lr != 1, the KL of order 1e-2.  ``edit(start, w)`` changes the start mask and the weights in place
+    (numpy, [T, N]) behind the columns made here; it draws nothing from the generator."""
     rng = np.random.RandomState(seed)
     dev = pol.flat_params.device
     S, A = pol.obs_dim, pol.action_dim
@@ -66,6 +67,9 @@ def _planes(pol, N, T, seed=3, at_old=False):
         start[18, 3 % N] = True                   # trailing weights = 0 segments (the rows behind a path that ended)
         w[20:, 3 % N] = 0.0
         w[T - 2:, 5 % N] = 0.0
+        start[0] = True
+    if edit is not None:
+        edit(start, w)
         start[0] = True
     start = torch.as_tensor(start, device=dev)
     w = torch.as_tensor(w, device=dev)

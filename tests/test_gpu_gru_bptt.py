@@ -48,14 +48,16 @@ def _policy(kind, hidden, seed=0, scale=0.1, **kw):
     return pol
 
 
-def _planes(pol, N, T, seed=3, at_old=False):
+def _planes(pol, N, T, seed=3, at_old=False, obs_scale=1.0, edit=None):
     """Synthetic planes in the order of npo_inputs.  ``at_old``: old == new (the point the Fisher matrix is taken at);
-    else the old means are the current ones plus a perturbation and the old log_std is moved: lr != 1, KL != 0."""
+    else the old means are the current ones plus a perturbation and the old log_std is moved: lr != 1, KL != 0.
+    ``obs_scale`` multiplies the observation planes; ``edit(start, w)`` changes the start mask and the weights in place
+    (numpy, [T, N]) behind the columns made here; neither draws from the generator."""
     rng = np.random.RandomState(seed)
     dev = pol.flat_params.device
     f = lambda *s: torch.as_tensor(rng.randn(*s).astype(np.float32), device=dev)
     Do, Da = pol.obs_dim, pol.action_dim
-    obs, act, adv = f(Do, T, N), 0.5 * f(Da, T, N), f(T, N)
+    obs, act, adv = obs_scale * f(Do, T, N), 0.5 * f(Da, T, N), f(T, N)
     start = rng.rand(T, N) < 0.08
     w = np.ones((T, N), dtype=np.float32)
     start[0] = True
@@ -67,6 +69,9 @@ def _planes(pol, N, T, seed=3, at_old=False):
         start[18, 3 % N] = True                   # trailing weights = 0 segments (the rows behind a path that ended)
         w[20:, 3 % N] = 0.0
         w[T - 2:, 5 % N] = 0.0
+        start[0] = True
+    if edit is not None:
+        edit(start, w)
         start[0] = True
     start = torch.as_tensor(start, device=dev)
     w = torch.as_tensor(w, device=dev)
