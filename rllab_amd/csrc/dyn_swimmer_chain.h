@@ -391,9 +391,12 @@ struct SwimChain {
         const R tz = -(s.om * (c.visc_ang + c.drag_ang * rl_abs(s.om)));
         const R tau = joint_torque(s.th, s.qd, act, c.lim_k, c.lim_b);
         const R taun = x.template qp<SHL1>(tau);
-        // force on the subtree hanging off this body's child joint = child's + grandchild's (the zero lane beyond)
-        const P fn = P{x.template qp<SHL1>(F.x) + x.template qp<SHL2>(F.x),
-                       x.template qp<SHL1>(F.y) + x.template qp<SHL2>(F.y)};
+        // force on the subtree hanging off this body's child joint = child's + grandchild's (the zero lane beyond):
+        // every lane adds its child's force to its own (one add with the lane move fused in; body 2 adds the zero
+        // lane's exact zero), and a body takes its CHILD's sum -- F_1 + F_2 for body 0, F_2 + 0 for body 1, the operands
+        // and the order of Fsx[1], Fsx[2] in the scalar program.  The move of fn.x rides in the product A.y * fn.x.
+        const P g = P{F.x + x.template qp<SHL1>(F.x), F.y + x.template qp<SHL1>(F.y)};
+        const P fn = qp2<SHL1>(x, g);
         const R Q = ((c.cxb * f.y + tz) + c.jxo * (A.x * fn.y - A.y * fn.x)) + (tau - taun);
         const P G = A * c.db;                                    // (Gx, Gy)
         const P Gp = Ap * c.db;                                  // (-Gy, Gx)
