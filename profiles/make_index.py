@@ -41,6 +41,9 @@ RECIPES = [
      "tools/exp/fvp_split_ab.py's loop with FVP_AB_WARM=400 FVP_AB_N=300 FVP_AB_READINGS=9, the parent as build/exp/lib_parent.so"),
     ("fvp_lds_tr_ab_bench.txt", "headline bench lines of the parent and the new library, interleaved, and their --dump-outputs compared", "tools/exp/lib_ab.py 'python bench.py --gpus 1 --steps 20 --warmup 3'"),
     ("fvp_lds_tr_*_pmc_product.csv", "one SQ counter pass over ten f16 split products at 2.048 M samples, parent / new library", "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE -- python tools/exp/fvp_splith_pmc.py 32"),
+    ("perp_ab_bench.jsonl", "rollout launch, iteration time and headline of the parent and the new library (Swimmer sub-step without a materialised perpendicular), alternating in one session, parent first and last",
+     "the two libraries swapped in place as tools/exp/lib_ab.py does, under 'python bench.py --gpus 1 --steps 20 --warmup 3', seven runs"),
+    ("perp_before_kernel_stats.csv", "rocprofv3 --kernel-trace --stats summary of `bench.py --steps 5 --warmup 2`, the parent of the perpendicular-operand change", "profiles/run_profile.sh perp swimmer4096_trpo perp_before stats"),
     ("r06_c11_policy_time.txt", "wide loss / gradient / product passes with (.orig) and without (lib_before_wpf) the one-tile-ahead prefetch", "tools/exp/r06_call11.sh"),
     ("r06_wide_kernel_bench.txt", "loss / gradient / product passes of the wide nets at the final sources", "python tools/kernel_bench.py --configs ..."),
     ("*_split_kernel_stats.csv", "kernel stats of the three Fisher-vector-product kernels back to back", "tools/prof_split.sh"),

@@ -5,10 +5,17 @@
 #   e.g.  profiles/run_profile.sh r04                                    (headline: swimmer4096_trpo -> r04_*)
 #         profiles/run_profile.sh r04 cheetah1024_trpo_gae r04_c5        (C5's per-GPU shard -> r04_c5_*)
 #         profiles/run_profile.sh r04 cartpole4096_vpg r04_c2            (C2 -> r04_c2_*)
+#         profiles/run_profile.sh ab swimmer4096_trpo ab_before stats    (the kernel-trace pass alone: one side of an A/B)
+#   Every pass runs under its own time limit and the recipe ends at the first pass that fails: nothing more is started
+#   on a device after a fault or a hang.
 ROUND=${1:-r04}
 WORKLOAD=${2:-swimmer4096_trpo}
 TAG=${3:-$ROUND}
+ONLY=${4:-all}
+rocprofv3() { timeout -k 10 420 rocprofv3 "$@"; }      # (timeout starts the program, not this function)
+python() { timeout -k 10 420 python "$@"; }
 case $WORKLOAD in cheetah1024_trpo_gae) NENVS=1024;; *) NENVS=4096;; esac
+set -eo pipefail
 set -x
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
@@ -18,6 +25,7 @@ BENCH="python bench.py --workload $WORKLOAD --steps 5 --warmup 2 --no-cpu-baseli
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -- $BENCH > gpurun_out/${TAG}_bench_under_rocprof.log 2>&1
 python profiles/summarize.py stats $P/stats gpurun_out/${TAG}_kernel_stats.csv
 head -12 gpurun_out/${TAG}_kernel_stats.csv
+if [ "$ONLY" = "stats" ]; then exit 0; fi
 BENCH2="python bench.py --workload $WORKLOAD --steps 2 --warmup 1 --no-cpu-baseline"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $P/fetch -- $BENCH2 > /dev/null 2>&1
 python profiles/summarize.py pmc $P/fetch gpurun_out/${TAG}_pmc_fetch_size.csv

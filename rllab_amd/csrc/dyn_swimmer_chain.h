@@ -9,7 +9,7 @@
 //                         lane runs the same instruction stream on its own body, values cross lanes by
 //                         quad-permute moves, the 3x3 solve is replicated.  Used by the fused rollout, where a lone
 //                         wavefront per SIMD pays 4 cycles per issued instruction: the per-env instruction stream
-//                         shrinks from ~260 to 89 per sub-step and four times as many wavefronts share the work.
+//                         shrinks from ~260 to 86 per sub-step and four times as many wavefronts share the work.
 //
 // Bit-exactness contract: every value the quad program computes is computed by the scalar program with the same
 // expression (same operands, same association, same statement boundaries -- the front-end contracts a*b+c only inside
@@ -301,8 +301,44 @@ struct SwimChain {
     // ---- quad program ------------------------------------------------------------------------------------------------
     // The x / y pairs of the planar dynamics travel as two-component vectors (rl_math.h V2): one v_pk_{mul,fma,add}_f32
     // per pair on gfx950 (5 cycles for a lone wavefront against 2 x 4 for the scalar forms), operand swizzles and
-    // broadcasts ride in op_sel.  Rotations use the body direction A = (cs, sn) and its perpendicular Ap = (-sn, cs), so
-    // that no component needs a separate sign flip:  R(a, b) = A a + Ap b,  R^-1(a, b) = Ap.yx a + A.yx b.
+    // broadcasts ride in op_sel.  Rotations use the body direction A = (cs, sn) and its perpendicular Ap = (-sn, cs):
+    // R(a, b) = A a + Ap b,  R^-1(a, b) = Ap.yx a + A.yx b.  Ap is never held in registers: a product with it is a
+    // product with A read through a swizzle, with the sign as a modifier on one half of one operand.  The sign of a
+    // product is the exclusive-or of its factors' signs and nothing else of the result depends on them, so (-a) * b,
+    // a * (-b) and -(a * b) are one float, also as the exact product inside a fused multiply-add: every product and every
+    // fused multiply-add below has the operands (up to that sign), the order and the bits it had with Ap materialised.
+    //   * times a SCALAR t the sign goes to the broadcast operand: the back-end folds the pair (-t, t) into neg_lo /
+    //     neg_hi of a broadcast (perp_mul, and (t, -t) where the product is the fused one);
+    //   * times one component of a PACKED result it folds neither form (it keeps a half-negated copy: v_xor + v_mov),
+    //     so the device build spells the one packed instruction out (perp_mul_y, perp_yx_fma_x).  The compiler pads no
+    //     wait states around an asm statement, and these two need none: their results feed plain vector arithmetic only
+    //     (perp_mul_y the fused multiply-add that forms F, perp_yx_fma_x the drag terms), never a lane move, and their
+    //     inputs are results of packed arithmetic, never of a transcendental.  The host build keeps plain C++ with the
+    //     same expression tree.
+    template <typename R>
+    RL_HD static V2<R> perp_mul(V2<R> a, R t) { return a.yx * V2<R>{-t, t}; }             // Ap * t = (-(a.y t), a.x t)
+    template <typename R>
+    RL_HD static V2<R> perp_mul_y(V2<R> a, V2<R> f) {                                       // Ap * f.yy
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (sizeof(R) == 4) {
+            V2<R> o;        // lo = (-a.y) f.y, hi = a.x f.y
+            asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,1] neg_lo:[1,0]" : "=v"(o) : "v"(a), "v"(f));
+            return o;
+        }
+#endif
+        return V2<R>{-a.y, a.x} * f.yy;
+    }
+    template <typename R>
+    RL_HD static V2<R> perp_yx_fma_x(V2<R> a, V2<R> v, V2<R> t) {                           // Ap.yx * v.xx + t, fused
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (sizeof(R) == 4) {
+            V2<R> o;        // lo = a.x v.x + t.x, hi = (-a.y) v.x + t.y
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] neg_hi:[1,0,0]" : "=v"(o) : "v"(a), "v"(v), "v"(t));
+            return o;
+        }
+#endif
+        return V2<R>{a.x, -a.y} * v.xx + t;
+    }
     // per-lane constants, selected by the lane's role b = lane & 3 (role 3: all zero)
     template <typename R>
     struct LaneConst {
@@ -343,11 +379,11 @@ struct SwimChain {
     }
     template <typename R>
     struct Lane {
-        V2<R> A, Ap;         // own body: (cs, sn) and (-sn, cs)   (role 3: A = (1, 0))
+        V2<R> A;             // own body: (cs, sn)   (role 3: A = (1, 0))
         V2<R> v, r;          // root velocity / position, replicated on the four lanes
         R om, th;            // absolute rate (role 3: 0, and stays 0 -- the other lanes read it as their zero), joint angle
         R qd;                // om - parent's om: the joint rate, carried from the end of the previous sub-step
-        RL_HD void set_direction(R cs, R sn) { A = V2<R>{cs, sn}; Ap = V2<R>{-sn, cs}; }
+        RL_HD void set_direction(R cs, R sn) { A = V2<R>{cs, sn}; }
     };
 
     // quad_perm controls: lane i of the quad reads lane P[i]
@@ -376,7 +412,7 @@ struct SwimChain {
     template <typename R, class X>
     RL_HD static void substep_quad(X& x, const LaneConst<R>& c, Lane<R>& s, R act, R h) {
         using P = V2<R>;
-        const P A = s.A, Ap = s.Ap;
+        const P A = s.A;
         const P oc = s.om * A;                                   // (ocs, osn)
         const P wl = oc.yx * c.kj;                               // (wlx, wly) = (-(osn jxo), ocs jxo)
         // cross-lane sums stay per component: each is one v_add_f32 with the quad-permute fused in
@@ -384,10 +420,11 @@ struct SwimChain {
                        (s.v.y + x.template qp<PAR1>(wl.y)) + x.template qp<PAR2>(wl.y)};
         const P vp = va + oc.yx * c.kc;                          // (vax - osn cxb, vay + ocs cxb)
         // body-frame velocity (vl, vt) = R^-1 vp, fluid force (fl, ft) along / across the body, world force F = R f
-        const P lt = Ap.yx * vp.xx + A.yx * vp.yy;
+        const P lty = A.yx * vp.yy;
+        const P lt = perp_yx_fma_x(A, vp, lty);                  // Ap.yx * vp.xx + A.yx * vp.yy
         const P m = P{c.visc_lin + c.kdrag.x * rl_abs(lt.x), c.visc_lin + c.kdrag.y * rl_abs(lt.y)};
         const P f = -(lt * m);
-        const P F = A * f.xx + Ap * f.yy;
+        const P F = A * f.xx + perp_mul_y(A, f);                 // A * f.xx + Ap * f.yy
         const R tz = -(s.om * (c.visc_ang + c.drag_ang * rl_abs(s.om)));
         const R tau = joint_torque(s.th, s.qd, act, c.lim_k, c.lim_b);
         const R taun = x.template qp<SHL1>(tau);
@@ -399,7 +436,6 @@ struct SwimChain {
         const P fn = qp2<SHL1>(x, g);
         const R Q = ((c.cxb * f.y + tz) + c.jxo * (A.x * fn.y - A.y * fn.x)) + (tau - taun);
         const P G = A * c.db;                                    // (Gx, Gy)
-        const P Gp = Ap * c.db;                                  // (-Gy, Gx)
         const R w2 = s.om * s.om;
         const P fw = F + w2 * G;
         const P sf = P{quad_sum(x, fw.x), quad_sum(x, fw.y)};
@@ -408,7 +444,7 @@ struct SwimChain {
         // coupling to the cyclic partner p; the pair (b, q) is partner q's own pair seen from the other side
         const P Pn = qp2<NX1>(x, A);
         const R w2p = x.template qp<NX1>(w2);
-        const P cds = Ap.yx * Pn.xx + A.yx * Pn.yy;              // (cos, sin)(phi_p - phi_b)
+        const P cds = A * P{Pn.x, -Pn.x} + A.yx * Pn.yy;         // Ap.yx * Pn.xx + A.yx * Pn.yy = (cos, sin)(phi_p - phi_b)
         const R Sbp = c.ksa.x * cds.x, tp = c.ksa.y * cds.y;     // (S_bp, t_bp)
         const P SS = P{Sbp, x.template qp<NX2>(Sbp)};            // (S_bp, S_bq)
         const R zc = w2 * tp;                                    // own rate^2 x own pair, fetched by the pair's other end
@@ -422,7 +458,7 @@ struct SwimChain {
         const R det = c.d_b * c0 + (SS.x * c12.x + SS.y * c12.y);
         const R num = c0 * rb + (c12.x * rp + c12.y * rq);
         const R thb = num * rl_recip_normal(det);
-        const P cp = Gp * thb;                                   // (cxp, cyp)
+        const P cp = perp_mul(G, thb);                           // (cxp, cyp) = (-(Gy thb), Gx thb)
         const P s2 = P{quad_sum(x, cp.x), quad_sum(x, cp.y)};
         const R hm = h * (R)INV_M;
         const P d = sf - s2;
@@ -435,8 +471,7 @@ struct SwimChain {
         const R dth = h * s.om;
         R sd, cd;
         rl_tiny_sincos(dth, sd, cd);
-        s.A = A * cd + Ap * sd;
-        s.Ap = P{-s.A.y, s.A.x};
+        s.A = A * cd + perp_mul(A, sd);                          // A * cd + Ap * sd
     }
 };
 
