@@ -425,6 +425,13 @@ typedef struct rl_gru_rollout_args {
 
 int rl_rollout_gaussian_gru(const rl_gru_rollout_args* args, void* stream);
 
+/* rl_rollout_gaussian_gru under DelayedActionEnv(action_delay): env i is stepped with the action its policy chose
+ * action_delay steps earlier in the same path (zeros before that); actions / means / the GRU's prev_action stay the
+ * policy's own.  action_queue: device float[action_delay][act_dim][n_envs], oldest first; read when
+ * reset_at_start == 0, written by every launch.  1 <= action_delay <= 16; a delay out of range or a null queue is
+ * RL_ERR_ARG, a queue that does not fit the LDS of a CU next to the weights and the hidden state RL_ERR_UNSUPPORTED. */
+int rl_rollout_gaussian_gru_delayed(const rl_gru_rollout_args* args, int32_t action_delay, float* action_queue, void* stream);
+
 /* The update of a GaussianGRUPolicy on the dense planes of a recurrent batch (csrc/gru_bptt_kernels.hip): surrogate loss
  * and mean KL of TRPO / TNPG, the flat gradient of the loss by back-propagation through time, and the product of the
  * Fisher matrix (the Hessian of the mean KL at new == old) with a vector.  Sample s = t * n_envs + i is step t of env

@@ -27,6 +27,7 @@ ENV_INVERTED_DOUBLE_PENDULUM = 7
 SYMBOLS = [
     "rl_last_error", "rl_abi_version", "rl_env_query", "rl_env_terminates", "rl_env_action_bounds", "rl_env_default_cfg", "rl_vecenv_com",
     "rl_vecenv_reset", "rl_vecenv_step", "rl_vecenv_step_graph", "rl_counter_add", "rl_vecenv_observe", "rl_rollout_gaussian_mlp", "rl_rollout_plan_query", "rl_rollout_lds_bytes", "rl_rollout_population", "rl_rollout_gaussian_gru",
+    "rl_rollout_gaussian_gru_delayed",
     "rl_gru_workspace_bytes", "rl_gru_gaussian_eval", "rl_gru_gaussian_grad", "rl_gru_gaussian_fvp",
     "rl_gru_categorical_workspace_bytes", "rl_gru_categorical_eval", "rl_gru_categorical_grad", "rl_gru_categorical_fvp",
     "rl_rollout_population_gru", "rl_gae",
@@ -294,6 +295,7 @@ def _load():
                                          ctypes.POINTER(ctypes.c_size_t)]
     lib.rl_rollout_population.argtypes = [ctypes.POINTER(PopulationArgs), vp]
     lib.rl_rollout_gaussian_gru.argtypes = [ctypes.POINTER(GruRolloutArgs), vp]
+    lib.rl_rollout_gaussian_gru_delayed.argtypes = [ctypes.POINTER(GruRolloutArgs), i32, vp, vp]
     lib.rl_rollout_population_gru.argtypes = [ctypes.POINTER(PopulationGruArgs), vp]
     lib.rl_gru_workspace_bytes.restype = ctypes.c_size_t
     lib.rl_gru_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]

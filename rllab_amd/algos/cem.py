@@ -78,6 +78,9 @@ def population_why_unsupported(env, policy, plot=False):
             return ("normalize(env, normalize_obs / normalize_reward): the running estimates of a NormalizedEnv are not "
                     "part of the population rollout")
         env = env._wrapped_env
+    if isinstance(getattr(env, "_base_env", None), HipEnv):
+        return ("%s: the task modifiers (OcclusionEnv / NoisyObservationEnv / DelayedActionEnv) are not part of the "
+                "population rollout" % type(env).__name__)
     if not isinstance(env, HipEnv):
         return "%s is not a HIP-native env (optionally wrapped in normalize)" % type(env).__name__
     if env._position_ids is not None:

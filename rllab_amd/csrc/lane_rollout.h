@@ -14,10 +14,20 @@
 //                                       carries from step to step (`reward` is the scaled one)
 //   finish(o)                           after the last step: save what resume() reads
 // and nothing of it should be alive across Env::step but what the next mean() needs.
+// Optional: static constexpr bool DELAYS_ACTIONS = true and
+//   delayed(act, applied)               the action the env is stepped with in place of the policy's own `act` (recorded,
+//                                       and handed to stepped(), as ever); once per step, ahead of Env::step
+// A policy without the member is compiled exactly as before.
 #pragma once
+#include <type_traits>
 #include "rollout_lane.h"
 
 namespace rl {
+
+template <class Policy, class = void>
+struct delays_actions : std::false_type {};
+template <class Policy>
+struct delays_actions<Policy, std::void_t<decltype(Policy::DELAYS_ACTIONS)>> : std::bool_constant<Policy::DELAYS_ACTIONS> {};
 
 // the by-value kernel arguments every such launch has
 struct LaneRolloutDev {
@@ -104,9 +114,17 @@ __device__ __forceinline__ void rollout_lane(const LaneRolloutDev& a, int i, Pol
 
         float r;
         bool d;
-        step_lane<Env>(s, act, a.normalize, a.cfg,
-                      a.act_noise_z ? a.act_noise_z + (size_t)t * DA * n : nullptr, n, i, a.seed, env_global,
-                      a.step_counter + (uint64_t)t, o, r, d);
+        if constexpr (delays_actions<Policy>::value) {
+            float applied[DA];
+            pol.delayed(act, applied);
+            step_lane<Env>(s, applied, a.normalize, a.cfg,
+                          a.act_noise_z ? a.act_noise_z + (size_t)t * DA * n : nullptr, n, i, a.seed, env_global,
+                          a.step_counter + (uint64_t)t, o, r, d);
+        } else {
+            step_lane<Env>(s, act, a.normalize, a.cfg,
+                          a.act_noise_z ? a.act_noise_z + (size_t)t * DA * n : nullptr, n, i, a.seed, env_global,
+                          a.step_counter + (uint64_t)t, o, r, d);
+        }
         ts += 1;
         if (a.max_path_length > 0 && ts >= a.max_path_length) d = true;
         const float rs = r * a.scale_reward;

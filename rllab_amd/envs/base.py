@@ -33,7 +33,8 @@ class Env(object):
     def spec(self):
         spec = self.__dict__.get("_cached_spec")
         if spec is None:
-            spec = EnvSpec(observation_space=self.observation_space, action_space=self.action_space)
+            spec = EnvSpec(observation_space=self.observation_space, action_space=self.action_space,
+                           sensor_rows=getattr(self, "sensor_rows", None))
             self.__dict__["_cached_spec"] = spec
         return spec
 

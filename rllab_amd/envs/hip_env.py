@@ -40,15 +40,20 @@ class HipVecEnv(object):
 
     def __init__(self, kind, n_envs, max_path_length, normalize=False, scale_reward=1.0, seed=None,
                  env_offset=0, action_space=None, observation_space=None, auto_reset=True, cfg=None,
-                 position_ids=None):
+                 position_ids=None, action_delay=0):
         """``cfg``: dict of env options (fields of ``rl_env_cfg``: ctrl_cost_coeff, alive_coeff, action_noise,
-        obs_noise, frame_skip, flags) on top of the env's defaults.  ``position_ids``: Box2DEnv(position_only=True)
-        -- the observation rows callers see (box2d_env.py:185-192,228-230); the kernels always produce the full
-        observation, the filter is a row selection of their output."""
+        obs_noise, frame_skip, flags) on top of the env's defaults.  ``position_ids``: Box2DEnv(position_only=True) /
+        OcclusionEnv -- the observation rows callers see (box2d_env.py:185-192,228-230); the kernels always produce the
+        full observation, the filter is a row selection of their output.  ``action_delay``: DelayedActionEnv -- every
+        env is stepped with the action it was handed ``action_delay`` steps earlier in the same path (zeros before
+        that); the executor owns the queue (``action_queue``)."""
         self.kind = kind
         self.cfg_overrides = dict(cfg or {})
         self.cfg = _lib.env_default_cfg(kind, **self.cfg_overrides)
         self.position_ids = None if position_ids is None else [int(i) for i in position_ids]
+        self.action_delay = int(action_delay)
+        if self.action_delay < 0:
+            raise ValueError("action_delay must be >= 0, got %r" % (action_delay,))
         self.n = int(n_envs)
         self.max_path_length = int(max_path_length) if max_path_length is not None else 0
         self.normalize = bool(normalize)
@@ -68,6 +73,15 @@ class HipVecEnv(object):
         self.step_counter = 0  # global step index: RNG counter base
         self._action_space, self._observation_space = action_space, observation_space
         self._pos_index = None if self.position_ids is None else torch.as_tensor(self.position_ids, device=self.device)
+        # DelayedActionEnv's queue, oldest first: [delay, Da, n]
+        self.action_queue = None if not self.action_delay else torch.zeros(
+            (self.action_delay, self.q["act_dim"], self.n), dtype=torch.float32, device=self.device)
+
+    @property
+    def graphable(self):
+        """Can the sampler's hipGraph loop drive this executor's buffers directly?  Not through an action queue, which
+        lives in ``step``."""
+        return not self.action_delay
 
     def __getstate__(self):
         d = dict(self.__dict__)
@@ -119,6 +133,30 @@ class HipVecEnv(object):
     def terminate(self):
         pass
 
+    # -- what the task modifiers set on the executor of the env they wrap (envs/occlusion_env.py, envs/noisy_env.py) ---
+    def keep_rows(self, ids, observation_space):
+        """OcclusionEnv: callers see rows ``ids`` of the FULL observation (already composed with position_only's)."""
+        self.position_ids = [int(i) for i in ids]
+        self._pos_index = torch.as_tensor(self.position_ids, device=self.device)
+        self._observation_space = observation_space
+        return self
+
+    def override_cfg(self, **overrides):
+        """NoisyObservationEnv: options of ``rl_env_cfg`` on top of the env's own."""
+        self.cfg_overrides.update(overrides)
+        self.cfg = _lib.env_default_cfg(self.kind, **self.cfg_overrides)
+        self.__dict__.pop("_plan_cache", None)
+        return self
+
+    def delay_actions(self, action_delay):
+        """DelayedActionEnv: a zeroed queue of ``action_delay`` actions per env."""
+        if int(action_delay) < 1:
+            raise ValueError("action_delay must be >= 1, got %r" % (action_delay,))
+        self.action_delay = int(action_delay)
+        self.action_queue = torch.zeros((self.action_delay, self.q["act_dim"], self.n), dtype=torch.float32,
+                                        device=self.device)
+        return self
+
     def reset(self, mask=None, draws=None, obs_noise_z=None):
         """Reset all envs (or those in ``mask``); returns obs_n as an [n, Do] view.  ``obs_noise_z`` [Do, n]:
         injected N(0,1) draws of the observation noise (parity runs; otherwise the in-kernel Philox stream)."""
@@ -133,16 +171,25 @@ class HipVecEnv(object):
             self.seed, self.step_counter, self.env_offset, self._cfg_with(None, oz), _lib.ptr(self._obs),
             _lib.stream_ptr()), "rl_vecenv_reset")
         self.step_counter += 1
+        if self.action_queue is not None:             # DelayedActionEnv.reset: an empty queue
+            if mask is None:
+                self.action_queue.zero_()
+            else:
+                self.action_queue.masked_fill_(mask.bool()[None, None, :], 0.0)
         return self._filtered(self._obs)
 
     def step(self, action_n, reset_draws=None, action_noise_z=None, obs_noise_z=None):
         """One lock-step transition.  ``action_n``: [n, Da] numpy array or tensor.
         numpy in -> numpy out; tensor in -> device tensors out (views of buffers
         that the next call overwrites).  ``action_noise_z`` [Da, n] / ``obs_noise_z`` [Do, n]: injected
-        N(0,1) draws of the env's own noises (parity runs)."""
+        N(0,1) draws of the env's own noises (parity runs).  With ``action_delay``: the envs are stepped with the head
+        of ``action_queue``, ``action_n`` is appended behind the rest and the columns of the envs that finished are
+        zeroed -- the per-transition definition of what rl_rollout_gaussian_gru_delayed does inside one launch."""
         is_np = not torch.is_tensor(action_n)
         a = torch.as_tensor(np.asarray(action_n) if is_np else action_n)
         a = a.to(device=self.device, dtype=torch.float32).reshape(self.n, self.q["act_dim"]).t().contiguous()
+        if self.action_queue is not None:
+            newest, a = a, self.action_queue[0].clone()
         if reset_draws is not None:
             reset_draws = torch.as_tensor(reset_draws, dtype=torch.float32, device=self.device).contiguous()
         az = self._plane(action_noise_z, (self.q["act_dim"], self.n))
@@ -154,6 +201,8 @@ class HipVecEnv(object):
             _lib.ptr(self._done), _lib.stream_ptr()), "rl_vecenv_step")
         self.step_counter += 1
         obs, rew, done = self._filtered(self._obs), self._reward, self._done.bool()
+        if self.action_queue is not None:
+            self.action_queue = torch.cat([self.action_queue[1:], newest[None]], dim=0).masked_fill_(done[None, None, :], 0.0)
         if is_np:
             return (obs.cpu().numpy().astype(np.float64), rew.cpu().numpy().astype(np.float64),
                     done.cpu().numpy(), dict())
@@ -193,16 +242,16 @@ class HipVecEnv(object):
         net on a 20-observation env needs 172 KB and is sampled through the per-transition loop instead."""
         if getattr(policy, "recurrent", False):
             return self._takes_recurrent_rollout_of(policy)
+        if self.action_delay:
+            return False                  # DelayedActionEnv: the queue rides in the recurrent rollout kernel only
         return self.rollout_plan(policy) is not None
 
     def _takes_recurrent_rollout_of(self, policy):
-        """A GaussianGRUPolicy with a rollout layout is sampled by rl_rollout_gaussian_gru; what that kernel does not
-        do on this executor is said in a sentence."""
+        """A GaussianGRUPolicy with a rollout layout is sampled by rl_rollout_gaussian_gru (under ``action_delay`` by
+        rl_rollout_gaussian_gru_delayed).  On kept rows (Box2DEnv(position_only=True), OcclusionEnv) the policy's kernel
+        layout is the one on the full observation, zero rows at the occluded entries (``GRUPolicyBase.pad_index``)."""
         if not hasattr(policy, "rollout_layout") or policy.rollout_layout() is None:
             return False
-        if self.position_ids is not None:
-            raise NotImplementedError("Box2DEnv(position_only=True) with a recurrent policy: the recurrent rollout kernel "
-                                      "feeds the GRU the full observation")
         return True
 
     def rollout_plan(self, policy, horizon=None, norm=None):
@@ -250,6 +299,9 @@ class HipVecEnv(object):
                                           "running estimates are not built into the recurrent rollout kernel")
             return self._rollout_recurrent(policy, horizon, reset_at_start, eps, reset_draws, action_noise_z, obs_noise_z,
                                            scale_reward)
+        if self.action_delay:
+            raise NotImplementedError("DelayedActionEnv: the action queue is built into the recurrent rollout kernel only; "
+                                      "a feed-forward policy is sampled through the per-transition path")
         if self.position_ids is not None and norm is not None:
             raise NotImplementedError("position_only observations under running normalisation: the estimates are over "
                                       "the kept rows; sample through the per-transition path")
@@ -333,14 +385,22 @@ class HipVecEnv(object):
                            scale_reward):
         """``rollout`` of a GaussianGRUPolicy (rl_rollout_gaussian_gru): the same planes and injected-noise keywords; the
         hidden state [H, n] and the previous action [Da, n] are buffers of this executor next to ``state`` / ``ts`` /
-        the last observation, written by every launch and read by one with ``reset_at_start=False``."""
+        the last observation, written by every launch and read by one with ``reset_at_start=False`` -- and so is
+        ``action_queue`` under ``action_delay`` (rl_rollout_gaussian_gru_delayed)."""
         if not self._takes_recurrent_rollout_of(policy):
             why = policy.why_no_rollout_kernel() if hasattr(policy, "why_no_rollout_kernel") else None
             raise NotImplementedError("no recurrent rollout kernel for this policy: %s" % (
                 why or "%s is not a GaussianGRUPolicy" % type(policy).__name__))
         T, n = int(horizon), self.n
         do, da = self.q["obs_dim"], self.q["act_dim"]
-        assert (policy.obs_dim, policy.action_dim) == (do, da), "policy built for another env"
+        if (policy.kernel_obs_dim, policy.action_dim) != (do, da) or policy.obs_dim != self.obs_rows:
+            raise ValueError("policy built for another env: the recurrent rollout of this executor takes a policy whose "
+                             "kernel layout is on %d observations (%d of them seen) and %d actions, this one's is on %d "
+                             "(%d) and %d" % (do, self.obs_rows, da, policy.kernel_obs_dim, policy.obs_dim,
+                                              policy.action_dim))
+        seen = list(range(do)) if policy.sensor_rows is None else list(policy.sensor_rows[1])
+        if seen != (list(range(do)) if self.position_ids is None else self.position_ids):
+            raise ValueError("policy built for other observation rows: %r, this executor keeps %r" % (seen, self.position_ids))
         H = policy.kernel_hidden
         theta = policy.rollout_layout()
         assert theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous()
@@ -373,8 +433,15 @@ class HipVecEnv(object):
             act_noise_z=None if az is None else az.data_ptr(), obs_noise_z=None if oz is None else oz.data_ptr(),
             obs=obs.data_ptr(), actions=act.data_ptr(), means=mean.data_ptr(), rewards=rew.data_ptr(),
             dones=done.data_ptr(), cfg=ctypes.pointer(self.cfg), opts=_lib.launch_opts())
-        _lib.check(_lib.lib.rl_rollout_gaussian_gru(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_gaussian_gru")
+        if self.action_delay:
+            _lib.check(_lib.lib.rl_rollout_gaussian_gru_delayed(ctypes.byref(args), self.action_delay,
+                                                                _lib.ptr(self.action_queue), _lib.stream_ptr()),
+                       "rl_rollout_gaussian_gru_delayed")
+        else:
+            _lib.check(_lib.lib.rl_rollout_gaussian_gru(ctypes.byref(args), _lib.stream_ptr()), "rl_rollout_gaussian_gru")
         self.step_counter += T + 1            # as rollout(): counter T belongs to the reset after the last step
+        if self._pos_index is not None:       # the batch holds what the policy saw: the kept rows
+            obs = obs.index_select(0, self._pos_index)
         return Trajectories(obs, act, mean, policy.recorded_log_std(), rew, done, self.max_path_length,
                             prev_action_info=bool(policy.state_include_action))
 
@@ -424,6 +491,9 @@ class HipVecEnv(object):
             prev_action_info=bool(include_action))
 
     def _population_shape(self, what, theta_pop, n_evals):
+        if self.action_delay:
+            raise NotImplementedError("%s under DelayedActionEnv: the action queue is built into the recurrent rollout "
+                                      "kernel only" % what)
         if self.position_ids is not None:
             raise NotImplementedError("%s on position_only observations: the candidates' first layers are "
                                       "built on the kept rows" % what)
@@ -507,6 +577,14 @@ class HipEnv(Env, Serializable):
     @property
     def observation_space(self):
         return self._observation_space
+
+    @property
+    def sensor_rows(self):
+        """``(full_obs_dim, kept rows)`` when callers see a selection of the kernels' observation
+        (Box2DEnv(position_only=True)), else None: what ``EnvSpec.sensor_rows`` carries to a recurrent policy."""
+        if self._position_ids is None:
+            return None
+        return int(self._q["obs_dim"]), tuple(int(i) for i in self._position_ids)
 
     @property
     def action_bounds(self):

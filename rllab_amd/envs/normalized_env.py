@@ -188,7 +188,7 @@ class NormalizingVecEnv(object):
                                                ("normalize_reward", self.normalize_reward)) if on)
             raise NotImplementedError("NormalizedEnv(%s=True) with a recurrent policy: the running estimates are not "
                                       "built into the recurrent rollout kernel (plain normalize(env) is)" % which)
-        if self.inner.position_ids is not None:
+        if self.inner.position_ids is not None or getattr(self.inner, "action_delay", 0):
             return False
         return self.inner.rollout_plan(policy, norm=(self.normalize_obs, self.normalize_reward)) is not None
 
@@ -209,7 +209,8 @@ class NormalizingVecEnv(object):
         to the lock step its batch is cut at, so the estimates are fed exactly once per sampled transition."""
         inner = self.inner
         return (self.obs_mean.clone(), self.obs_var.clone(), self.reward_mean.clone(), self.reward_var.clone(),
-                inner.state.clone(), inner.ts.clone(), inner._obs.clone(), inner.step_counter)
+                inner.state.clone(), inner.ts.clone(), inner._obs.clone(), inner.step_counter,
+                None if getattr(inner, "action_queue", None) is None else inner.action_queue.clone())
 
     def restore(self, snap):
         inner = self.inner
@@ -217,6 +218,8 @@ class NormalizingVecEnv(object):
                                 inner._obs), snap):
             mine.copy_(saved)
         inner.step_counter = snap[7]
+        if snap[8] is not None:                       # DelayedActionEnv's queue (HipVecEnv.action_queue)
+            inner.action_queue = snap[8].clone()
 
     def write_back(self, env):
         """Env copy 0's estimates -> the NormalizedEnv that gets pickled (its ``_obs_mean`` / ``_obs_var`` state)."""

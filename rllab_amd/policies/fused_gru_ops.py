@@ -42,7 +42,7 @@ class RecurrentOpsBase(object):
         idx, size = policy.pad_index()
         self.n_flat, self.n_kernel = int(policy.flat_params.numel()), int(size)
         assert idx.size == self.n_flat
-        self.index = None if policy.hidden_dim == policy.kernel_hidden else \
+        self.index = None if policy.kernel_layout_is_flat else \
             torch.as_tensor(idx, dtype=torch.long, device=dev)
         frozen = [np.arange(p.offset, p.offset + p.size) for p in policy.get_params() if not p.tags.get("trainable", False)]
         self.frozen = torch.as_tensor(np.concatenate(frozen), dtype=torch.long, device=dev) if frozen else None
@@ -190,15 +190,19 @@ class FusedGRUOps(RecurrentOpsBase):
 
     def __init__(self, policy):
         RecurrentOpsBase.__init__(self, policy)
-        self.dims = (int(policy.obs_dim), int(policy.action_dim), int(policy.kernel_hidden),
+        self.dims = (int(policy.kernel_obs_dim), int(policy.action_dim), int(policy.kernel_hidden),
                      int(policy.state_include_action))
+        # a policy on kept observation rows: the batch's [k, T, N] planes go to their rows of zeroed [Do, T, N] planes
+        self.obs_rows = None if policy.sensor_rows is None else \
+            torch.as_tensor(policy.sensor_rows[1], dtype=torch.long, device=policy.flat_params.device)
+        self.batch_obs_dim = int(policy.obs_dim)
 
     def accepts(self, inputs):
         """A recurrent Gaussian batch of [., T, N] planes on the device with ONE old log_std row.  A tuple that is not one
         falls back to autograd inside the optimizer, behind init_opt's ``update path: HIP kernels`` line: the log says so,
         once per tuple."""
         b = Batch._make(inputs) if len(inputs) == len(Batch._fields) else None
-        ok = b is not None and b.obs.is_cuda and b.obs.dim() == 3 and b.obs.shape[0] == self.dims[0] \
+        ok = b is not None and b.obs.is_cuda and b.obs.dim() == 3 and b.obs.shape[0] == self.batch_obs_dim \
             and b.old_log_std.numel() == self.dims[1] and not D.is_distributed()
         key = id(inputs[0]) if len(inputs) else 0
         if not ok and getattr(self, "_refused_key", None) != key:
@@ -216,6 +220,11 @@ class FusedGRUOps(RecurrentOpsBase):
                 named.start.to(torch.uint8).contiguous(), named.weights.to(f32).contiguous()]
         do, da, H, inc = self.dims
         T, N = int(named.obs.shape[1]), int(named.obs.shape[2])
+        if self.obs_rows is not None:
+            # the occluded rows are zeros that meet zero weight rows; their gradient / product entries are never gathered
+            full = torch.zeros((do, T, N), dtype=f32, device=keep[0].device)
+            full.index_copy_(0, self.obs_rows.to(full.device), keep[0])
+            keep[0] = full
         need = _lib.lib.rl_gru_workspace_bytes(N, T, do, da, H, inc)
         if need == 0:
             raise RuntimeError("rl_gru_workspace_bytes: %s" % _lib.lib.rl_last_error().decode())

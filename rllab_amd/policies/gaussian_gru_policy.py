@@ -42,6 +42,14 @@ class GaussianGRUPolicy(GRUPolicyBase, StochasticPolicy, Serializable):
         assert len(hidden_sizes) == 1
         self.obs_dim = env_spec.observation_space.flat_dim
         self.action_dim = env_spec.action_space.flat_dim
+        # built on kept rows of a HIP-native env's observation (OcclusionEnv, position_only): the kernels run the policy
+        # on the full observation, zero weight rows at the occluded entries (GRUPolicyBase.pad_index)
+        self._sensor_rows = getattr(env_spec, "sensor_rows", None)
+        if self._sensor_rows is not None:
+            full, ids = self._sensor_rows
+            if len(ids) != self.obs_dim or len(set(ids)) != len(ids) or not all(0 <= i < full for i in ids):
+                raise ValueError("env_spec.sensor_rows = %r does not name %d distinct rows of a %d-entry observation" % (
+                    self._sensor_rows, self.obs_dim, full))
         self._state_include_action = bool(state_include_action)
         self.input_dim = self.obs_dim + (self.action_dim if self._state_include_action else 0)
         self.hidden_dim = int(hidden_sizes[0])
@@ -144,7 +152,7 @@ class GaussianGRUPolicy(GRUPolicyBase, StochasticPolicy, Serializable):
         if not self.flat_params.is_cuda or self.flat_params.dtype != torch.float32:
             return "the parameters are not float32 on a HIP device"
         from rllab_amd import _lib
-        if _lib.lib.rl_gru_workspace_bytes(64, 1, self.obs_dim, self.action_dim, self.kernel_hidden,
+        if _lib.lib.rl_gru_workspace_bytes(64, 1, self.kernel_obs_dim, self.action_dim, self.kernel_hidden,
                                            int(self._state_include_action)) == 0:
             return _lib.lib.rl_last_error().decode()
         return None
@@ -169,9 +177,9 @@ class GaussianGRUPolicy(GRUPolicyBase, StochasticPolicy, Serializable):
                 self.hidden_nonlinearity, "__name__", repr(self.hidden_nonlinearity))
         if self.output_nonlinearity is not None:
             return "output_nonlinearity is not None (the recurrent rollout kernel's output layer is linear)"
-        if self.obs_dim > MAX_OBS_DIM or self.action_dim > MAX_ACT_DIM:
-            return "obs_dim %d / action_dim %d exceed the kernels' %d / %d" % (self.obs_dim, self.action_dim, MAX_OBS_DIM,
-                                                                             MAX_ACT_DIM)
+        if self.kernel_obs_dim > MAX_OBS_DIM or self.action_dim > MAX_ACT_DIM:
+            return "obs_dim %d / action_dim %d exceed the kernels' %d / %d" % (self.kernel_obs_dim, self.action_dim,
+                                                                             MAX_OBS_DIM, MAX_ACT_DIM)
         if not self.flat_params.is_cuda or self.flat_params.dtype != torch.float32:
             return "the parameters are not float32 on a HIP device"
         return None

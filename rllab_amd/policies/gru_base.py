@@ -203,15 +203,35 @@ class GRUPolicyBase(object):
         """The hidden width the kernel runs this policy at: the next of 32 / 64."""
         return next((H for H in KERNEL_HIDDEN if self.hidden_dim <= H), None)
 
+    @property
+    def sensor_rows(self):
+        """``(full_obs_dim, ids)`` of a policy built on kept observation rows (``EnvSpec.sensor_rows``), else None."""
+        return getattr(self, "_sensor_rows", None)
+
+    @property
+    def kernel_obs_dim(self):
+        """The observation width the kernels run this policy at: the env's full observation under ``sensor_rows``."""
+        return self.obs_dim if self.sensor_rows is None else self.sensor_rows[0]
+
+    @property
+    def kernel_layout_is_flat(self):
+        """True when the kernels' parameter vector IS the flat one: no hidden unit padded, no observation row occluded."""
+        return self.hidden_dim == self.kernel_hidden and self.sensor_rows is None
+
     def pad_index(self):
         """Index of every parameter inside the kernel's vector: the same order with the hidden axis zero-padded to
         ``kernel_hidden``.  Exact: a padded unit has zero weights and bias, so c = tanh(0) = 0, it starts at h0 = 0 and
-        h' = (1 - u) 0 + u 0 stays 0; its outgoing weights are 0."""
+        h' = (1 - u) 0 + u 0 stays 0; its outgoing weights are 0.
+        Under ``sensor_rows = (full_obs_dim, ids)`` the input axis of W_x* is laid out on the env's full observation too:
+        kept row j goes to row ids[j], the previous-action rows go behind ``full_obs_dim``, the rows of the occluded
+        observations stay zero -- products with 0, in the kernel's input-index order the kept rows' sums are unchanged."""
         H, Hp = self.hidden_dim, self.kernel_hidden
+        sensor = self.sensor_rows
         idx, off = [], 0
         for name, shape, _, _ in self._specs(H):
             rows = 1 if len(shape) == 1 else shape[0]
             cols = shape[-1]
+            row_at = np.arange(rows)
             if name in _NO_HIDDEN_AXIS:
                 rows_p, cols_p = 1, cols
             elif name == "output.W":
@@ -220,16 +240,21 @@ class GRUPolicyBase(object):
                 rows_p, cols_p = Hp, Hp
             else:                                   # h0, b_*: one row; W_x*: one row per input
                 rows_p, cols_p = rows, Hp
-            r, c = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+                if sensor is not None and name.startswith("W_x"):
+                    kept = len(sensor[1])
+                    rows_p = rows - kept + sensor[0]
+                    row_at = np.concatenate([np.asarray(sensor[1], dtype=np.int64), sensor[0] + np.arange(rows - kept)])
+            r, c = np.meshgrid(row_at, np.arange(cols), indexing="ij")
             idx.append((off + r * cols_p + c).reshape(-1))
             off += rows_p * cols_p
         return np.concatenate(idx), off
 
     def pack_rows(self, xs):
         """Parameter ROWS [n_cand, P] (float32, device) -> kernel-layout rows [n_cand, P_pad], row c what
-        ``rollout_layout()`` holds after ``set_param_values(xs[c])``: zeros at the padded hidden units (a population of
+        ``rollout_layout()`` holds after ``set_param_values(xs[c])``: zeros at the padded hidden units and the occluded
+        observation rows (a population of
         candidates: ``HipVecEnv.rollout_population_recurrent``)."""
-        if self.hidden_dim == self.kernel_hidden:
+        if self.kernel_layout_is_flat:
             return xs
         idx, size = self.pad_index()
         out = torch.zeros((xs.shape[0], size), dtype=xs.dtype, device=xs.device)
@@ -241,7 +266,7 @@ class GRUPolicyBase(object):
         recurrent rollout kernel does not run this policy (``why_no_rollout_kernel()`` says why)."""
         if self.why_no_rollout_kernel() is not None:
             return None
-        if self.hidden_dim == self.kernel_hidden:
+        if self.kernel_layout_is_flat:
             return self.flat_params.detach()
         lay = getattr(self, "_rollout_layout", None)
         if lay is None:

@@ -93,7 +93,9 @@ class VectorizedSampler(BaseSampler):
             return "fused rollout kernel (one launch per batch of %d envs)" % ve.n, None
         if ve is None:
             return "none (no executor yet)", None
-        if not getattr(ve, "graphable", True) and ve.position_ids is not None:
+        if getattr(ve, "action_delay", 0):
+            why = "DelayedActionEnv: the action queue is built into the recurrent rollout kernel only"
+        elif not getattr(ve, "graphable", True) and ve.position_ids is not None:
             why = "Box2DEnv(position_only=True) under NormalizedEnv(normalize_obs / normalize_reward): the running " \
                   "estimates are over the kept rows, the fused rollout's over the full observation"
         elif not getattr(ve, "graphable", True):
