@@ -1023,6 +1023,46 @@ int rl_peer_allreduce_sum(int n, double* data, int rank, int world, void* const*
                                                                  * silent peer after 10 s of wall clock only; > 0 also after
                                                                  * that many polls (tests of the give-up path) */
 
+/* ---- DDPG: K whole updates in one launch (rllab/algos/ddpg.py:267-365) ----------------------------------------------
+ * One workgroup runs n_updates updates back to back -- batch rows, target values, the Q step, the policy step at the Q
+ * parameters just written, the soft target updates -- with the parameters kept on the chip in between
+ * (csrc/ddpg_kernels.hip).  K updates in one launch and K launches of one update give the same bits.
+ *   shapes   obs_dim <= 32, act_dim <= 8, two hidden layers of 1 .. 64 units (padded to 32 / 64 in `state`), hidden
+ *            activation RL_ACT_TANH / RL_ACT_RECTIFY, policy output RL_ACT_TANH / RL_ACT_IDENTITY, Q merges the action
+ *            in front of hidden layer 1, 1 <= batch <= 128, 1 <= n_updates <= 16384; size > batch
+ *   state    device buffer of the size the state_bytes query below returns, float32: theta[P], targets[P], Adam m[P],
+ *            v[P], scratch[P], then two int32 step counts (Q, policy).  Each plane = [policy | Q]; a net =
+ *            W0[in][H0p] b0 W1[in1][H1p] b1 W2[H1p][out] b2, W row-major [in][out], H0p / H1p = hidden sizes padded to
+ *            32 or 64 with zeros; Q's W1 has H0p hidden rows followed by act_dim action rows
+ *   pool     float32 planes obs[cap][D], act[cap][A], rew[cap], term[cap], next_obs[cap][D], skip[cap]; the newest
+ *            `size` rows end before row `top`
+ *   indices  int32 [n_updates][batch] pool rows (clamped into the pool), or NULL: drawn in the kernel -- slot b of
+ *            update update_base + u takes word 0 of Philox4x32-10 at counters (attempt, b, c_lo, c_hi), key seed;
+ *            row = (top - size + ((word * size) >> 32)) mod capacity; a row with skip = 1 is redrawn with the next
+ *            attempt, after 32 attempts the first kept row forward (mod size) is taken
+ *   methods  0 adam (lasagne.updates.adam: beta1 0.9, beta2 0.999, epsilon 1e-8, t carried in `state`), 1 sgd
+ *   stats    NULL or double[16], ADDED to: sum qf_loss, sum policy surr, updates, sum q, sum |q|, sum y, sum |y|,
+ *            sum |q - y|, samples
+ *   indices_out / q_out / y_out   NULL or [n_updates][batch]: the rows used, Q(s, a) before the step, the targets y
+ * Argument errors return RL_ERR_ARG / RL_ERR_UNSUPPORTED before anything is launched. */
+typedef struct rl_ddpg_args {
+    int32_t obs_dim, act_dim, hidden0, hidden1;
+    int32_t hidden_activation, output_activation;   /* enum rl_activation */
+    int32_t batch, n_updates;
+    int32_t capacity, size, top;
+    int32_t qf_method, policy_method;
+    int32_t reserved;
+    float discount, tau, qf_learning_rate, policy_learning_rate, qf_weight_decay, policy_weight_decay;
+    uint64_t seed, update_base;
+    void* state;
+    const void *obs, *act, *rew, *term, *next_obs, *skip;
+    const void* indices;
+    void *indices_out, *stats, *q_out, *y_out;
+} rl_ddpg_args;
+
+size_t rl_ddpg_state_bytes(int obs_dim, int act_dim, int hidden0, int hidden1);   /* 0: a shape the kernel does not run */
+int rl_ddpg_update(const rl_ddpg_args* args, void* stream);
+
 /* Debug / test hook: fill out[4*count] with Philox4x32-10 blocks for counters
  * (c0 + i, c1, c2, c3), key (k0, k1), i = 0..count-1.  Device buffer. */
 int rl_debug_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,

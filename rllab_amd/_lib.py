@@ -39,7 +39,7 @@ SYMBOLS = [
     "rl_peer_allreduce_sum",
     "rl_mlp_forward", "rl_mlp_forward_ws", "rl_mlp_backward", "rl_gaussian_head_workspace_bytes", "rl_gaussian_head", "rl_gaussian_fisher",
     "rl_rollout_gridworld", "rl_rollout_gridworld_gru", "rl_categorical_softmax", "rl_categorical_head_workspace_bytes", "rl_categorical_head",
-    "rl_categorical_fisher", "rl_cmaes_cov_update",
+    "rl_categorical_fisher", "rl_cmaes_cov_update", "rl_ddpg_state_bytes", "rl_ddpg_update",
 ]
 
 
@@ -164,6 +164,27 @@ class GridWorldGruArgs(ctypes.Structure):
         ("obs", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("prob_out", ctypes.c_void_p),
         ("rewards", ctypes.c_void_p), ("dones", ctypes.c_void_p),
     ]
+
+
+class DdpgArgs(ctypes.Structure):
+    """Mirror of ``rl_ddpg_args`` (include/rllab_amd.h): K DDPG updates on a device replay pool in one launch."""
+    _fields_ = [
+        ("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("hidden0", ctypes.c_int32), ("hidden1", ctypes.c_int32),
+        ("hidden_activation", ctypes.c_int32), ("output_activation", ctypes.c_int32), ("batch", ctypes.c_int32),
+        ("n_updates", ctypes.c_int32), ("capacity", ctypes.c_int32), ("size", ctypes.c_int32), ("top", ctypes.c_int32),
+        ("qf_method", ctypes.c_int32), ("policy_method", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("discount", ctypes.c_float), ("tau", ctypes.c_float), ("qf_learning_rate", ctypes.c_float),
+        ("policy_learning_rate", ctypes.c_float), ("qf_weight_decay", ctypes.c_float),
+        ("policy_weight_decay", ctypes.c_float), ("seed", ctypes.c_uint64), ("update_base", ctypes.c_uint64),
+        ("state", ctypes.c_void_p), ("obs", ctypes.c_void_p), ("act", ctypes.c_void_p), ("rew", ctypes.c_void_p),
+        ("term", ctypes.c_void_p), ("next_obs", ctypes.c_void_p), ("skip", ctypes.c_void_p),
+        ("indices", ctypes.c_void_p), ("indices_out", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+        ("q_out", ctypes.c_void_p), ("y_out", ctypes.c_void_p),
+    ]
+
+
+DDPG_ADAM, DDPG_SGD = 0, 1
+DDPG_STATS = 16            # doubles in rl_ddpg_args.stats
 
 
 class PolicyBatch(ctypes.Structure):
@@ -354,6 +375,9 @@ def _load():
     lib.rl_categorical_head.argtypes = [sz, i32, vp, vp, vp, vp, vp, f32, i32, f32, vp, vp, sz, vp, vp]
     lib.rl_categorical_fisher.argtypes = [sz, i32, vp, vp, vp, f32, vp, vp]
     lib.rl_cmaes_cov_update.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rl_ddpg_state_bytes.restype = sz
+    lib.rl_ddpg_state_bytes.argtypes = [i32, i32, i32, i32]
+    lib.rl_ddpg_update.argtypes = [vp, vp]
     vpp = ctypes.POINTER(ctypes.c_void_p)
     lib.rl_peer_mailbox_bytes.restype = sz
     lib.rl_peer_mailbox_bytes.argtypes = [i32, i32]
