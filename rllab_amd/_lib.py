@@ -274,7 +274,6 @@ def launch_opts():
     v = e("RLLAB_FVP_SPLIT_WPS")
     o.fvp_split_wps = int(v[0]) if v and v[0] in "134" else 0
     o.lfb_valu = 1 if e("RLLAB_LFB_VALU") is not None else 0
-    o.reserved[0] = _env_int("RLLAB_SPLIT16_ABLATE", range(1, 8))     # timing ablations of fvp_split16_kernel (wrong results)
     return ctypes.addressof(o)
 
 

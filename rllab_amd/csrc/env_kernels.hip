@@ -1961,6 +1961,7 @@ static int plan_rollout(const rl_rollout_args* g, rl_rollout_plan* p) {
     const int n = g->n_envs, T = g->horizon;
     const int cfg_flags = g->cfg ? g->cfg->flags : 0;
     plan_fill(p, RL_ROLLOUT_UNSUPPORTED, 0, 0, 0, 0, "");
+    if (int rc = check_opts(g->opts, "rl_rollout_gaussian_mlp / rl_rollout_plan_query")) return rc;
     char nm[96];
     const bool equal = g->hidden2 == 0 && g->hidden0 == g->hidden1 && (g->hidden0 == 32 || g->hidden0 == 64);
     WideShape act_probe;
@@ -2100,17 +2101,6 @@ static int plan_rollout(const rl_rollout_args* g, rl_rollout_plan* p) {
     return RL_OK;
 }
 
-// hipFuncSetAttribute once per kernel (dynamic LDS beyond 64 KB)
-template <class K>
-static int allow_big_lds(K kern, bool& done) {
-    if (done) return 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    done = true;
-    return 0;
-}
-
 template <class Env>
 static int launch_rollout(const rl_rollout_args* g, hipStream_t st) {
     if constexpr (has_mjc<Env>::value && !is_mjc_env<Env>::value) {
@@ -2159,10 +2149,10 @@ static int launch_rollout(const rl_rollout_args* g, hipStream_t st) {
             const size_t mean_floats = RolloutPolicyWide<Env>::lds_floats(shape, 64 * pl.wavefronts_per_workgroup);
             static bool a16 = false, a64 = false;
             if (epw == 16) {
-                if ((rc = allow_big_lds(rollout_dual_kernel<Env, 16>, a16))) return rc;
+                if ((rc = allow_dynamic_lds(rollout_dual_kernel<Env, 16>, 160 * 1024, a16))) return rc;
                 hipLaunchKernelGGL((rollout_dual_kernel<Env, 16>), grid, block, lds, st, a, shape, sshape, g->theta_std, (int)mean_floats);
             } else {
-                if ((rc = allow_big_lds(rollout_dual_kernel<Env, 64>, a64))) return rc;
+                if ((rc = allow_dynamic_lds(rollout_dual_kernel<Env, 64>, 160 * 1024, a64))) return rc;
                 hipLaunchKernelGGL((rollout_dual_kernel<Env, 64>), grid, block, lds, st, a, shape, sshape, g->theta_std, (int)mean_floats);
             }
             break;
@@ -2180,10 +2170,10 @@ static int launch_rollout(const rl_rollout_args* g, hipStream_t st) {
         case RL_ROLLOUT_WIDE: {
             static bool a16 = false, a64 = false;
             if (epw == 16) {
-                if ((rc = allow_big_lds(rollout_wide_kernel<Env, 16>, a16))) return rc;
+                if ((rc = allow_dynamic_lds(rollout_wide_kernel<Env, 16>, 160 * 1024, a16))) return rc;
                 hipLaunchKernelGGL((rollout_wide_kernel<Env, 16>), grid, block, lds, st, a, shape);
             } else {
-                if ((rc = allow_big_lds(rollout_wide_kernel<Env, 64>, a64))) return rc;
+                if ((rc = allow_dynamic_lds(rollout_wide_kernel<Env, 64>, 160 * 1024, a64))) return rc;
                 hipLaunchKernelGGL((rollout_wide_kernel<Env, 64>), grid, block, lds, st, a, shape);
             }
             break;
@@ -2205,13 +2195,13 @@ static int launch_rollout(const rl_rollout_args* g, hipStream_t st) {
                 }
                 if (pl.kernel == RL_ROLLOUT_SWIMMER_QUAD_COOP) {
                     static bool ca = false;
-                    if ((rc = allow_big_lds(rollout_swimmer_quad_coop_kernel, ca))) return rc;
+                    if ((rc = allow_dynamic_lds(rollout_swimmer_quad_coop_kernel, 160 * 1024, ca))) return rc;
                     hipLaunchKernelGGL(rollout_swimmer_quad_coop_kernel, grid, block, lds, st, a, shape);
                     break;
                 }
                 if (pl.kernel == RL_ROLLOUT_SWIMMER_QUAD_WIDE) {
                     static bool wa = false;
-                    if ((rc = allow_big_lds(rollout_swimmer_quad_wide_kernel, wa))) return rc;
+                    if ((rc = allow_dynamic_lds(rollout_swimmer_quad_wide_kernel, 160 * 1024, wa))) return rc;
                     hipLaunchKernelGGL(rollout_swimmer_quad_wide_kernel, grid, block, lds, st, a, shape);
                     break;
                 }
@@ -2233,7 +2223,7 @@ static int launch_rollout(const rl_rollout_args* g, hipStream_t st) {
                 }
                 if (pl.kernel == RL_ROLLOUT_TWO_LEG_QUAD_WIDE) {
                     static bool ta = false;
-                    if ((rc = allow_big_lds(rollout_two_leg_quad_wide_kernel<Env>, ta))) return rc;
+                    if ((rc = allow_dynamic_lds(rollout_two_leg_quad_wide_kernel<Env>, 160 * 1024, ta))) return rc;
                     hipLaunchKernelGGL((rollout_two_leg_quad_wide_kernel<Env>), grid, block, lds, st, a, shape);
                     break;
                 }

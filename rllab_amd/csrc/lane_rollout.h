@@ -54,6 +54,7 @@ template <class Env, class Args>
 static int lane_rollout_dev(const Args* g, long long n, const char* entry, const char* kernel, LaneRolloutDev& a) {
     // the widest plane [obs_dim][T][n] is addressed with size_t, a ROW of n floats with 32-bit byte offsets
     if (n > (1ll << 29)) return set_error(RL_ERR_ARG, "%s: %lld envs (at most 2^29)", entry, n);
+    if (int rc = check_opts(g->opts, entry)) return rc;
     a.n = (int)n; a.T = g->horizon; a.max_path_length = g->max_path_length; a.normalize = g->normalize;
     a.env_offset = g->env_offset; a.scale_reward = g->scale_reward; a.seed = g->seed; a.step_counter = g->step_counter;
     a.state = g->state; a.ts = g->ts; a.eps = g->eps; a.reset_draws = g->reset_draws;

@@ -36,15 +36,11 @@
 // float64 in a fixed order, as in the other families.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "../../include/rllab_amd.h"
-#include "capi_util.h"
-#include "policy_mfma.h"
+#include "fvp_split_common.h"
 #include "policy_wide.h"
 
 namespace rl {
 
-int launch_reduce_rows(const float* partial, int rows, int cols, double* out, hipStream_t st);   // policy_kernels.hip
-bool net_has_narrow_kernel(int obs_dim, int act_dim, int h0, int h1, int h2);                    // policy_kernels.hip
 
 namespace cs {
 
@@ -931,18 +927,7 @@ static int launch(const CsShape& s, const rl_policy_batch* g, const float* vec, 
     int grid = 256 * per_cu;
     if (grid > n_tiles) grid = n_tiles;
     if (grid > CS_MAX_GRID) grid = CS_MAX_GRID;
-    auto kern = csplit_fvp_kernel<L, WW, MT, SHP>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WW * WV), s.lds_total, st, a);
-    rc = check_launch("csplit_fvp_kernel");
-    if (rc) return rc;
-    return launch_reduce_rows(a.partial, grid, s.P, out, st);
+    return launch_partial_rows<csplit_fvp_kernel<L, WW, MT, SHP>>("csplit_fvp_kernel", a, grid, WW * WV, 160 * 1024, s.lds_total, s.P, out, st);
 }
 
 template <int L>

@@ -39,10 +39,8 @@
 // Roofline: MFMA-bound.  FVP = 94 MFMAs (H = 32, swimmer) per 32-sample tile = 6016 matrix
 // cycles per SIMD; HBM sees each sample's 80 B once per pass.
 #include <hip/hip_runtime.h>
-#include "../../include/rllab_amd.h"
-#include "capi_util.h"
 #include "cg_device.h"
-#include "policy_mfma.h"
+#include "fvp_split_common.h"
 
 namespace rl {
 
@@ -826,12 +824,6 @@ int wide_dispatch(int mode, const rl_policy_batch* g, const float* vec, void* ws
                   hipStream_t st, double* loss_out, const float* cot = nullptr, float* out_mean = nullptr,
                   float* out_dmean = nullptr);                       // policy_wide_kernels.hip
 struct WideShape;
-// policy_split_kernels.hip: the cached Fisher-vector product of the 32-unit nets on the bf16 matrix pipe (three-way
-// split operands, f32 accuracy); RL_SPLIT_NOT_TAKEN when the launch is not its to make
-int split_fvp_dispatch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st);
-int splith_fvp_dispatch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st);
-int csplit_fvp_dispatch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st);
-size_t csplit_workspace_bytes_for(int obs_dim, int act_dim, int h0, int h1, int h2);   // 0 = not its shape
 size_t wide_workspace_bytes_for(int obs_dim, int act_dim, int h0, int h1, int h2);   // 0 = not a wide shape
 
 struct PlaneArgs {                 // MODE_OUT / MODE_OUT_TAN / MODE_BWD
@@ -887,14 +879,10 @@ static int launch_pass(const rl_policy_batch* g, const float* vec, void* workspa
                                          : (with_loss ? (double*)((char*)workspace + row_bytes) : nullptr);
     auto kern = policy_pass_kernel<N, MODE, CACHE, RELU, ACTS>;
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    int rc = allow_dynamic_lds(kern, (int)lds, attr_set);
+    if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * WV), lds, st, a);
-    int rc = check_launch("policy_pass_kernel");
+    rc = check_launch("policy_pass_kernel");
     if (rc) return rc;
     if (OUTMODE) return 0;
     if (MODE == MODE_LOSS) {
@@ -952,19 +940,36 @@ static int dispatch_relu(int mode, const rl_policy_batch* g, void* ws, size_t ws
     return set_error(RL_ERR_UNSUPPORTED, "rectify networks: only the loss and the log-likelihood gradient are built");
 }
 
-// (obs_dim, act_dim, H) of the one-wavefront-per-tile kernels (two equal tanh layers): every HIP-native env's pair at 32
-// and 64 units + the one-output value nets.  Everything else runs on the cooperative kernels -- and the two families
-// cache their activations in different layouts, which is what the split Fisher-vector products ask this for.
-#define RL_NARROW_NETS(X) \
-    X(4, 1, 32) X(6, 1, 32) X(11, 1, 32) X(13, 2, 32) X(20, 3, 32) X(20, 6, 32) X(21, 6, 32) \
-    X(4, 1, 64) X(6, 1, 64) X(11, 1, 64) X(13, 2, 64) X(20, 3, 64) X(20, 6, 64) X(21, 6, 64) \
-    X(13, 1, 32) X(20, 1, 32) X(21, 1, 32)
 bool net_has_narrow_kernel(int d, int k, int h0, int h1, int h2) {
     if (h2 != 0) return false;
 #define NARROWCASE(DO, DA, H) if (d == DO && k == DA && h0 == H && h1 == H) return true;
     RL_NARROW_NETS(NARROWCASE)
 #undef NARROWCASE
     return false;
+}
+
+// The split-operand kernels of a cached Fisher-vector product in the ORDER they are asked: rl_policy_fvp launches on the first
+// that takes the batch and leaves the launch to it, rl_policy_fvp_variant reports that one's number; nobody takes it: the f32
+// matrix instructions below (variant 0).
+static bool split16_on_request(const rl_policy_batch* g) {     // an A/B variant: never the library's choice
+    return g->opts && g->opts->fvp_split == 3 && split_fvp_takes(g) && split16_fvp_takes(g);
+}
+static const struct FvpKernel {
+    bool (*takes)(const rl_policy_batch* g);
+    int (*dispatch)(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st);
+    int variant;
+} FVP_KERNELS[] = {
+    {split16_on_request, split16_fvp_dispatch, 3},   // 16-sample tiles, three or four wavefronts per SIMD
+    {splith_fvp_takes, splith_fvp_dispatch, 4},      // two-way f16 split (obs_absmax set): (32, 32) and (64, 64)
+    {split_fvp_takes, split_fvp_dispatch, 1},        // three-way bf16 split: the same shapes, one wavefront per tile
+    {csplit_fvp_takes, csplit_fvp_dispatch, 2},      // cooperative: nets with a 128-unit layer, 64-unit and deep nets on request
+};
+static int fvp_split_dispatch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st) {
+    for (const FvpKernel& k : FVP_KERNELS) {
+        const int rc = k.takes(g) ? k.dispatch(g, vec, ws, ws_bytes, out, st) : RL_SPLIT_NOT_TAKEN;
+        if (rc != RL_SPLIT_NOT_TAKEN) return rc;
+    }
+    return RL_SPLIT_NOT_TAKEN;
 }
 
 static int dispatch_net(int mode, const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes,
@@ -985,10 +990,7 @@ static int dispatch_net(int mode, const rl_policy_batch* g, const float* vec, vo
 #define PLANECASE(DO, DA, H) \
         if (all_tanh && g->hidden2 == 0 && d == DO && k == DA && h0 == H && h1 == H) \
             return dispatch_planes<Net<DO, DA, H>>(mode, g, vec, ws, ws_bytes, out, st, pl);
-        PLANECASE(4, 1, 32) PLANECASE(6, 1, 32) PLANECASE(11, 1, 32) PLANECASE(13, 2, 32) PLANECASE(20, 3, 32)
-        PLANECASE(20, 6, 32) PLANECASE(21, 6, 32)
-        PLANECASE(4, 1, 64) PLANECASE(6, 1, 64) PLANECASE(11, 1, 64) PLANECASE(13, 2, 64) PLANECASE(20, 3, 64)
-        PLANECASE(20, 6, 64) PLANECASE(21, 6, 64)
+        RL_PLANE_NETS(PLANECASE)
 #undef PLANECASE
         // anything else with two or three tanh layers of 32 / 64 / 128 units: the cooperative kernels, whose operand
         // images need the caller's workspace (rl_mlp_forward_ws; rl_mlp_backward always had one)
@@ -1004,7 +1006,7 @@ static int dispatch_net(int mode, const rl_policy_batch* g, const float* vec, vo
         if (!all_tanh)
             return set_error(RL_ERR_UNSUPPORTED, "three hidden layers: tanh layers only (the cooperative kernels)");
         if (mode == MODE_FVP) {
-            const int rc = csplit_fvp_dispatch(g, vec, ws, ws_bytes, out, st);    // split-operand arithmetic (cached products)
+            const int rc = fvp_split_dispatch(g, vec, ws, ws_bytes, out, st);     // (only the cooperative kernel takes three layers)
             if (rc != RL_SPLIT_NOT_TAKEN) return rc;
         }
         return wide_dispatch(mode, g, vec, ws, ws_bytes, out, st, loss_out);
@@ -1020,11 +1022,7 @@ static int dispatch_net(int mode, const rl_policy_batch* g, const float* vec, vo
     if (g->kl_penalty != 0.0f && mode != MODE_VPG && mode != MODE_GRAD)
         return set_error(RL_ERR_ARG, "rl_policy_batch.kl_penalty applies to the gradient passes only");
     if (mode == MODE_FVP && cg == nullptr && all_tanh) {
-        int rc = splith_fvp_dispatch(g, vec, ws, ws_bytes, out, st);         // two-way f16 split (obs_absmax set)
-        if (rc != RL_SPLIT_NOT_TAKEN) return rc;
-        rc = split_fvp_dispatch(g, vec, ws, ws_bytes, out, st);              // (32, 32): one wavefront per tile
-        if (rc != RL_SPLIT_NOT_TAKEN) return rc;
-        rc = csplit_fvp_dispatch(g, vec, ws, ws_bytes, out, st);             // 64-unit and wide nets: cooperative
+        const int rc = fvp_split_dispatch(g, vec, ws, ws_bytes, out, st);
         if (rc != RL_SPLIT_NOT_TAKEN) return rc;
     }
 #define NETCASE(DO, DA, H) \
@@ -1130,7 +1128,16 @@ extern "C" int rl_policy_fvp(const rl_policy_batch* g, const float* vec, void* w
     int rc = check_batch(g, "rl_policy_fvp");
     if (rc) return rc;
     if (!vec || !fvp_out) return set_error(RL_ERR_ARG, "rl_policy_fvp: bad argument");
+    if ((rc = check_opts(g->opts, "rl_policy_fvp"))) return rc;
     return dispatch_net(MODE_FVP, g, vec, workspace, workspace_bytes, fvp_out, (hipStream_t)stream);
+}
+
+extern "C" int rl_policy_fvp_variant(const rl_policy_batch* g) {
+    if (!g) return set_error(RL_ERR_ARG, "rl_policy_fvp_variant: null batch");
+    if (int rc = check_opts(g->opts, "rl_policy_fvp_variant")) return rc;
+    for (const FvpKernel& k : FVP_KERNELS)
+        if (k.takes(g)) return k.variant;
+    return 0;
 }
 
 extern "C" int rl_mlp_forward(const rl_policy_batch* g, const float* vec, float* out, float* dout, void* stream) {

@@ -27,20 +27,14 @@
 // matrix pipe (tools/ubench/mfma_bf16_valu_overlap.hip; MI355X_MICROARCH.md "price of one filler beside MFMAs").
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "../../include/rllab_amd.h"
-#include "capi_util.h"
-#include "policy_mfma.h"
+#include "fvp_split_common.h"
 
 namespace rl {
-
-int launch_reduce_rows(const float* partial, int rows, int cols, double* out, hipStream_t st);   // policy_kernels.hip
 
 namespace split16 {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -48,17 +42,12 @@ constexpr int H = 32;
 constexpr int T16 = 16;                 // samples per tile
 // wavefronts per SIMD: 4 (128 registers) or 3 (168); one workgroup of 4 WPS wavefronts per CU
 
-// build-time switch: the residual a - bf16(a) of a pair as two v_dot2c_f32_bf16 (policy_split_kernels.hip's
-// RL_SPLIT_DOT2: 7 instead of 11 instructions per pair) -- off: dot instructions cost the matrix pipe of the SIMD
-#ifndef RL_SPLIT16_DOT2
-#define RL_SPLIT16_DOT2 0
-#endif
-// build-time switch: residual subtractions and element-wise stages on packed-f32 instructions (two values per issue slot).
-// The kernel is bound by the SUM of its issue slots at three / four wavefronts per SIMD (profiles/r06_notes.md section 6),
-// so fewer slots are worth more than the overlap packed instructions forgo.
-#ifndef RL_SPLIT16_PK
-#define RL_SPLIT16_PK 1
-#endif
+// Settled, once build-time switches: the residual a - bf16(a) of a pair stays on plain / packed subtractions -- the two
+// v_dot2c_f32_bf16 of policy_split_kernels.hip (RL_SPLIT16_DOT2: 7 instead of 11 instructions per pair) lost, dot instructions cost
+// the matrix pipe of the SIMD -- and the residual subtractions and element-wise stages stay on packed-f32 instructions, two
+// values per issue slot (RL_SPLIT16_PK; the alternative was one plain instruction per value): the kernel is bound by the SUM of
+// its issue slots at three / four wavefronts per SIMD (profiles/r06_notes.md section 6), so fewer slots are worth more than the
+// overlap packed instructions forgo.
 
 struct Args {
     int B;
@@ -70,9 +59,13 @@ struct Args {
     float inv_count;
     float log_min_std;
     float* partial;            // [grid][P]
-    int ablate;                // timing ablations (rl_launch_opts.reserved[0], WRONG results): 1 = the tile loop re-uses the first
-                               // tile's cached fragments, 2 = ... its observations / weight (no LDS-direct pieces in the loop)
 };
+
+// Timing ablation (WRONG results, default off; tools/exp/fvp_split16_time.py): 1 = the tile loop re-uses the first tile's cached
+// fragments, 2 = ... its observations / weight, 3 = both (no LDS-direct pieces in the loop): what the loads cost
+#ifndef RL_ABL_SPLIT16_FETCH
+#define RL_ABL_SPLIT16_FETCH 0
+#endif
 
 struct Parts { u32x4 p[3]; };                  // hi, mid, lo of eight values (bf16 pairs)
 struct TParts { unsigned v[3][2]; };           // a transposed block: [part][pair of samples]
@@ -103,52 +96,26 @@ __device__ __forceinline__ f32x4 outer6(const TParts& A, const TParts& B, f32x4 
 __device__ __forceinline__ unsigned cvt_pk(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
-#if RL_SPLIT16_DOT2
-__device__ __forceinline__ bf16x2 dot2_selector(unsigned bits) {      // (in a register: policy_split_kernels.hip's finding)
-    unsigned v;
-    asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(bits));
-    return __builtin_bit_cast(bf16x2, v);
-}
-#endif
 // (a0, a1) - their packed bf16 rounding h, exact
 __device__ __forceinline__ void residual(float a0, float a1, unsigned h, float& r0, float& r1) {
-#if RL_SPLIT16_DOT2
-    const bf16x2 e0 = dot2_selector(0x0000bf80u), e1 = dot2_selector(0xbf800000u);
-    r0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, h), e0, a0, false);
-    r1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, h), e1, a1, false);
-#elif RL_SPLIT16_PK
     const f32x2 r = f32x2{a0, a1} - f32x2{__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};
     r0 = r[0]; r1 = r[1];
-#else
-    r0 = a0 - __uint_as_float(h << 16);
-    r1 = a1 - __uint_as_float(h & 0xffff0000u);
-#endif
 }
 // element-wise helpers over register pairs
 __device__ __forceinline__ void pk_dtanh(const float (&h)[8], float (&dz)[8]) {          // dz = 1 - h h
-#if RL_SPLIT16_PK
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const f32x2 hh = {h[2 * j], h[2 * j + 1]};
         const f32x2 d = __builtin_elementwise_fma(-hh, hh, f32x2{1.0f, 1.0f});
         dz[2 * j] = d[0]; dz[2 * j + 1] = d[1];
     }
-#else
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dz[i] = __builtin_fmaf(-h[i], h[i], 1.0f);
-#endif
 }
 __device__ __forceinline__ void pk_mul(const f32x4 (&acc)[2], const float (&d)[8], float (&out)[8]) {   // out = acc d
-#if RL_SPLIT16_PK
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const f32x2 p = f32x2{acc[j >> 1][2 * (j & 1)], acc[j >> 1][2 * (j & 1) + 1]} * f32x2{d[2 * j], d[2 * j + 1]};
         out[2 * j] = p[0]; out[2 * j + 1] = p[1];
     }
-#else
-#pragma unroll
-    for (int i = 0; i < 8; ++i) out[i] = acc[i >> 2][i & 3] * d[i];
-#endif
 }
 // x = hi + mid + lo, each a bf16: successive round-to-nearest residuals; written stage by stage over the four pairs
 // of a fragment (independent instructions next to each other)
@@ -420,7 +387,7 @@ __global__ void __launch_bounds__(4 * WPS * WV) fvp_split16_kernel(Args a) {
             for (int e = 0; e < 4; ++e) { h1[e] = v0[e]; h1[4 + e] = v1[e]; }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        fetch(nxt, a.ablate);
+        fetch(nxt, RL_ABL_SPLIT16_FETCH);
         const float c = wgt * a.inv_count;
         float dz1[8], dg[8], gmu[DA];                                       // dg: dh1, then gz1
         pk_dtanh(h1, dz1);
@@ -430,7 +397,6 @@ __global__ void __launch_bounds__(4 * WPS * WV) fvp_split16_kernel(Args a) {
             float W2r[8], dW2r[8];
             row8(k * 8, W2r);
             row8((DA + k) * 8, dW2r);
-#if RL_SPLIT16_PK
             f32x2 q0 = {0.0f, 0.0f}, q1 = {0.0f, 0.0f};                     // two chains of pairs
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -439,14 +405,6 @@ __global__ void __launch_bounds__(4 * WPS * WV) fvp_split16_kernel(Args a) {
             }
             const f32x2 q = q0 + q1;
             const float p0 = q[0], p1 = q[1];
-#else
-            float p0 = 0.0f, p1 = 0.0f;                                     // two chains
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                p0 = __builtin_fmaf(h1[i], dW2r[i], p0);
-                p1 = __builtin_fmaf(dg[i], W2r[i], p1);
-            }
-#endif
             const float dmu = db2[k] + group_sum(p0 + p1);
             gmu[k] = c * dmu * fk[k];
         }
@@ -463,7 +421,6 @@ __global__ void __launch_bounds__(4 * WPS * WV) fvp_split16_kernel(Args a) {
         for (int k = 0; k < DA; ++k) {
             float W2r[8];
             row8(k * 8, W2r);
-#if RL_SPLIT16_PK
             const f32x2 gk = {gmu[k], gmu[k]};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -472,15 +429,7 @@ __global__ void __launch_bounds__(4 * WPS * WV) fvp_split16_kernel(Args a) {
                 const f32x2 w = __builtin_elementwise_fma(f32x2{h1[2 * j], h1[2 * j + 1]}, gk, f32x2{gW2l[2 * j][k], gW2l[2 * j + 1][k]});
                 gW2l[2 * j][k] = w[0]; gW2l[2 * j + 1][k] = w[1];
             }
-#else
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                dg[i] = __builtin_fmaf(W2r[i], gmu[k], dg[i]);
-                gW2l[i][k] = __builtin_fmaf(h1[i], gmu[k], gW2l[i][k]);
-            }
-#endif
         }
-#if RL_SPLIT16_PK
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const f32x2 d = f32x2{dg[2 * j], dg[2 * j + 1]} * f32x2{dz1[2 * j], dz1[2 * j + 1]};
@@ -488,13 +437,6 @@ __global__ void __launch_bounds__(4 * WPS * WV) fvp_split16_kernel(Args a) {
             const f32x2 b = f32x2{gb1l[2 * j], gb1l[2 * j + 1]} + d;
             gb1l[2 * j] = b[0]; gb1l[2 * j + 1] = b[1];
         }
-#else
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            dg[i] *= dz1[i];
-            gb1l[i] += dg[i];
-        }
-#endif
         stage();
         Parts G1s;
         split8(dg, G1s);
@@ -585,56 +527,22 @@ __global__ void __launch_bounds__(4 * WPS * WV) fvp_split16_kernel(Args a) {
 #pragma unroll
         for (int k = 0; k < DA; ++k) {
             myrow[N::B2 + k] = b2s[k];
-            // log_std block of the Fisher: d2KL/ds2 = 4 v (2 v - eps) / (2 v + eps)^2, v = sigma^2
-            const float vv = var_[k], e = 1e-8f;
-            const float cc = floored[k] ? 0.0f : 4.0f * vv * (2.0f * vv - e) / ((2.0f * vv + e) * (2.0f * vv + e));
-            myrow[N::LSTD + k] = cc * vc[N::LSTD + k] * ws;
+            myrow[N::LSTD + k] = log_std_fisher(var_[k], floored[k]) * vc[N::LSTD + k] * ws;
         }
     }
     __syncthreads();
-    float* row = a.partial + (size_t)blockIdx.x * P;
-    for (int k = threadIdx.x; k < P; k += WAVES * WV) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) t += reinterpret_cast<const float*>(smem)[w * P + k];
-        row[k] = t;
-    }
+    fold_rows<WAVES, P>(smem, a.partial);
 }
 
 template <int DO, int DA, int WPS>
 static int launch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st) {
-    using S = Shape<DO, DA, WPS>;
-    using N = typename S::N;
-    constexpr int WAVES = S::WAVES;
-    Args a;
-    a.B = g->n_samples; a.theta = g->theta; a.vec = vec; a.acts = g->activations; a.obs = g->obs; a.weight = g->weights;
-    a.inv_count = g->inv_count; a.log_min_std = g->log_min_std;
-    a.ablate = g->opts ? g->opts->reserved[0] : 0;
-    const int n_tiles = a.B / T16;
-    int grid = (n_tiles + WAVES - 1) / WAVES;
-    if (grid > 256) grid = 256;                   // one workgroup per CU, WPS wavefronts per SIMD
-    const size_t need = (size_t)grid * N::P * sizeof(float);
-    if (ws_bytes < need) return set_error(RL_ERR_ARG, "policy pass workspace too small: %zu < %zu bytes", ws_bytes, need);
-    a.partial = (float*)ws;
-    auto kern = fvp_split16_kernel<DO, DA, WPS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           S::LDS_TOTAL);
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * WV), S::LDS_TOTAL, st, a);
-    int rc = check_launch("fvp_split16_kernel");
-    if (rc) return rc;
-    return launch_reduce_rows(a.partial, grid, N::P, out, st);
+    using S = Shape<DO, DA, WPS>;                  // WPS wavefronts per SIMD
+    return launch_tiles<fvp_split16_kernel<DO, DA, WPS>, S::WAVES, T16, S::LDS_TOTAL, S::N::P>("fvp_split16_kernel", make_args<Args>(g, vec),
+                                                                                             ws, ws_bytes, out, st);
 }
 
 }  // namespace split16
 
-// (obs_dim, act_dim) pairs of the HIP-native envs whose (32, 32) policy has at most two actions (the per-lane sums of the
-// output layer's outer product are 8 act_dim registers of the 128)
-#define SPLIT16_SHAPES(X) X(4, 1) X(6, 1) X(11, 1) X(13, 2) X(13, 1)
 bool split16_fvp_takes(const rl_policy_batch* g) {
     if (!g->activations || g->hidden2 != 0 || g->hidden0 != 32 || g->hidden1 != 32 || g->activation != RL_ACT_TANH ||
         g->layer_activations != 0 || g->n_samples <= 0 || g->n_samples % TS != 0)

@@ -30,20 +30,14 @@
 // rows) are staged in LDS once per workgroup and read per use.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "../../include/rllab_amd.h"
-#include "capi_util.h"
-#include "policy_mfma.h"
+#include "fvp_split_common.h"
 
 namespace rl {
-
-int launch_reduce_rows(const float* partial, int rows, int cols, double* out, hipStream_t st);   // policy_kernels.hip
 
 namespace split {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -111,65 +105,38 @@ __device__ __forceinline__ f32x16 mm6(const Parts& A, const Parts& B, f32x16 c) 
     return c;
 }
 
-// value + the value of the same sample in the other lane half, without an LDS round trip (v_permlane32_swap)
-__device__ __forceinline__ float half_sum_swap(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// Build-time switches of the round-5 instruction diet (tools/exp/r05_split_variants.sh times each against the other):
-//   RL_SPLIT_DOT2  the residual  a - bf16(a)  of a pair as two v_dot2c_f32_bf16 (packed rounding x (-1, 0) / (0, -1),
-//                  accumulated onto a) instead of two unpack instructions + one packed subtraction: every term is exactly
-//                  representable, so the dot product is the same number (tools/ubench/dot2_residual.hip checks it bit
-//                  for bit on the device, denormal residuals included)
-//   RL_SPLIT_PK    the element-wise stages (tanh derivatives, the output layer's thin products, bias sums) on packed
-//                  f32 instructions, two values per issue slot
-#ifndef RL_SPLIT_DOT2
-#define RL_SPLIT_DOT2 1
-#endif
-#ifndef RL_SPLIT_PK
-#define RL_SPLIT_PK 1
-#endif
-//   RL_SPLIT_SCALAR_SUB  (with RL_SPLIT_DOT2 = 0) the residual as two plain v_sub_f32 instead of one v_pk_add_f32: packed
-//                  f32 instructions of one wavefront do not overlap the matrix instructions of another
-//                  (tools/ubench/mfma_bf16_valu_overlap.hip, profiles/r03_notes.md), plain ones do
-//   RL_SPLIT_ASM_DMA  the LDS-direct loads of the next tile's cached activations as inline asm.  Issued through the
-//                  builtin, the compiler has to assume that they write ANY LDS address and puts s_waitcnt vmcnt(0) in
-//                  front of the next LDS read it cannot tell apart -- the output layer's rows, a third of the way into
-//                  the tile: the wavefront then sits out the rest of the HBM round trip it had meant to hide
-//                  (timing ablation RL_ABL_FETCH: 19 % of the kernel).  The asm form is invisible to that pass; the
-//                  loop's own s_waitcnt vmcnt(0) at the top of the next tile is the (only) wait the data needs.
-#ifndef RL_SPLIT_SCALAR_SUB
-#define RL_SPLIT_SCALAR_SUB 0
-#endif
-//   RL_SPLIT_BULK_ROWS  (with RL_SPLIT_PK; round 6) the output layer's rows of a lane half come in bulk -- per action the
-//                  16 rows of W2 and of its tangent are eight 16-byte LDS reads issued together and waited for once -- and
-//                  its per-lane dot products run as FOUR independent packed partial sums.  By the ISA of the round-5 build
-//                  this stage was one chain of 16 dependent v_pk_fma_f32 per action (a wait state behind every one) with a
-//                  ds_read_b128 + s_waitcnt lgkmcnt(0) in front of every other one: ~20 exposed LDS round trips per tile
-//                  (fvp_split64_kernel got this form in round 5; the 32-unit kernel had not).
-#ifndef RL_SPLIT_BULK_ROWS
-#define RL_SPLIT_BULK_ROWS 1
-#endif
-//   RL_SPLIT_OPS_AHEAD  (two wavefronts per SIMD: operand blocks in LDS; round 6) the three parts of the NEXT operand block
+// Settled experiments of rounds 5 and 6, once build-time switches of this file; what stayed is the code below, what lost is gone:
+//   RL_SPLIT_DOT2 (kept)  the residual  a - bf16(a)  of a pair as two v_dot2c_f32_bf16 (packed rounding x (-1, 0) / (0, -1),
+//                  accumulated onto a): every term is exactly representable, so the dot product is the same number
+//                  (tools/ubench/dot2_residual.hip checks it bit for bit on the device, denormal residuals included).  The
+//                  alternative was two unpack instructions + one packed subtraction (profiles/r05_notes.md section 1.2).
+//   RL_SPLIT_PK (kept)  the element-wise stages (tanh derivatives, the output layer's thin products, bias sums) on packed f32
+//                  instructions, two values per issue slot; the alternative was one plain instruction per value (same section).
+//   RL_SPLIT_SCALAR_SUB (dropped)  without the dot form, the residual as two plain v_sub_f32 instead of one v_pk_add_f32, because
+//                  packed f32 instructions of one wavefront do not overlap the matrix instructions of another
+//                  (tools/ubench/mfma_bf16_valu_overlap.hip, profiles/r03_notes.md); tools/exp/r05_split_variants.sh timed it
+//                  against the dot form, which stayed.
+//   RL_SPLIT_ASM_DMA (kept)  the LDS-direct loads of the next tile's inputs as inline asm.  Issued through the builtin, the
+//                  compiler has to assume that they write ANY LDS address and puts s_waitcnt vmcnt(0) in front of the next
+//                  LDS read it cannot tell apart -- the output layer's rows, a third of the way into the tile: the wavefront
+//                  then sits out the rest of the HBM round trip it had meant to hide (timing ablation RL_ABL_FETCH: 19 % of
+//                  the kernel).  The asm form is invisible to that pass; the loop's own s_waitcnt vmcnt(0) at the top of the
+//                  next tile is the (only) wait the data needs.  The alternative kept observations and weight in registers.
+//   RL_SPLIT_BULK_ROWS (kept; round 6)  the output layer's rows of a lane half come in bulk -- per action the 16 rows of W2 and
+//                  of its tangent are eight 16-byte LDS reads issued together and waited for once -- and its per-lane dot
+//                  products run as FOUR independent packed partial sums.  By the ISA of the round-5 build this stage was one
+//                  chain of 16 dependent v_pk_fma_f32 per action (a wait state behind every one) with a ds_read_b128 +
+//                  s_waitcnt lgkmcnt(0) in front of every other one: ~20 exposed LDS round trips per tile
+//                  (profiles/r06_notes.md section 7; fvp_split64_kernel had this form since round 5).
+//   RL_SPLIT_OPS_AHEAD (kept; round 6)  two wavefronts per SIMD, operand blocks in LDS: the three parts of the NEXT operand block
 //                  are read before the six products of the current one are issued (and the first block of a chain before
-//                  the vector work in front of it): by the ISA every block was read right in front of its use and
-//                  waited for -- seven exposed LDS round trips per tile
-#ifndef RL_SPLIT_OPS_AHEAD
-#define RL_SPLIT_OPS_AHEAD 1
-#endif
-//   RL_SPLIT_FILL  (with RL_SPLIT_OPS_AHEAD; round 6) vector work that does not depend on a chain of products is issued INSIDE
-//                  it: a v_mfma_f32_32x32x16_bf16 occupies the matrix pipe for 8 passes and leaves ~5 issue slots of its
-//                  own wavefront free (MI355X_MICROARCH.md), which a chain of six dependent products otherwise wastes.  The
-//                  split of dh0 (needed by the chain after next) rides inside dW1^T h0.  MEASURED: nothing (0.2117 - 0.2149 ms
-//                  with the filler on dot / packed or on plain instructions against 0.2095 - 0.2147 without, same box,
-//                  profiles/r06_notes.md section 7) and 17 spilled registers -- off.
-#ifndef RL_SPLIT_FILL
-#define RL_SPLIT_FILL 0
-#endif
-#ifndef RL_SPLIT_ASM_DMA
-#define RL_SPLIT_ASM_DMA 1
-#endif
+//                  the vector work in front of it); by the ISA every block was read right in front of its use and waited
+//                  for -- seven exposed LDS round trips per tile (same section).
+//   RL_SPLIT_FILL (dropped; round 6)  vector work that does not depend on a chain of products (the split of dh0, on plain
+//                  instructions) issued INSIDE the chain dW1^T h0, in the ~5 issue slots a v_mfma_f32_32x32x16_bf16 leaves its
+//                  own wavefront.  MEASURED: nothing (0.2117 - 0.2149 ms with the filler on dot / packed or on plain
+//                  instructions against 0.2095 - 0.2147 without, same box, profiles/r06_notes.md section 7) and 17 spilled
+//                  registers.
 // a - h for a pair a and its packed bf16 rounding h (exact)
 // The two selectors (-1, 0) and (0, -1) travel in REGISTERS: handed to the instruction as a constant, (-1, 0) is encoded as
 // the inline constant "-1.0", which the VOP2 form of v_dot2c_f32_bf16 reads as the f32 pattern 0xbf800000 = (0, -1) --
@@ -182,17 +149,8 @@ __device__ __forceinline__ bf16x2 dot2_selector(unsigned bits) {
     return __builtin_bit_cast(bf16x2, v);
 }
 __device__ __forceinline__ f32x2 residual(f32x2 a, bf16x2 h) {
-#if RL_SPLIT_DOT2
     const bf16x2 e0 = dot2_selector(0x0000bf80u), e1 = dot2_selector(0xbf800000u);
     return f32x2{__builtin_amdgcn_fdot2_f32_bf16(h, e0, a[0], false), __builtin_amdgcn_fdot2_f32_bf16(h, e1, a[1], false)};
-#elif RL_SPLIT_SCALAR_SUB
-    const f32x2 hf = __builtin_convertvector(h, f32x2);
-    float r0 = a[0] - hf[0], r1 = a[1] - hf[1];
-    asm volatile("" : "+v"(r0), "+v"(r1));           // (keeps the two subtractions apart: no re-packing)
-    return f32x2{r0, r1};
-#else
-    return a - __builtin_convertvector(h, f32x2);
-#endif
 }
 // x = hi + mid + lo, each a bf16: successive round-to-nearest residuals (every subtraction is exact)
 __device__ __forceinline__ void split_pair(float a0, float a1, Parts& out, int j) {
@@ -225,20 +183,6 @@ __device__ __forceinline__ void split_pair(float a0, float a1, Parts& out, int j
     out.p[0][j] = h[0]; out.p[0][j + 1] = h[1];
     out.p[1][j] = m[0]; out.p[1][j + 1] = m[1];
     out.p[2][j] = q[0]; out.p[2][j + 1] = q[1];
-}
-// the same split on PLAIN vector instructions (v_cvt_pk_bf16_f32, v_lshlrev_b32, v_and_b32, v_sub_f32): the form that runs in
-// the issue slots a matrix instruction of the same wavefront leaves free -- packed-f32 and dot instructions cost extra
-// cycles beside the matrix pipe (MI355X_MICROARCH.md: "price of one filler beside MFMAs")
-__device__ __forceinline__ void split_pair_plain(float a0, float a1, Parts& out, int j) {
-    const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a0, a1}, bf16x2));
-    const float r0 = a0 - __uint_as_float(h << 16), r1 = a1 - __uint_as_float(h & 0xffff0000u);
-    const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-    const float l0 = r0 - __uint_as_float(m << 16), l1 = r1 - __uint_as_float(m & 0xffff0000u);
-    const unsigned q = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{l0, l1}, bf16x2));
-    const bf16x2 hh = __builtin_bit_cast(bf16x2, h), mm = __builtin_bit_cast(bf16x2, m), qq = __builtin_bit_cast(bf16x2, q);
-    out.p[0][j] = hh[0]; out.p[0][j + 1] = hh[1];
-    out.p[1][j] = mm[0]; out.p[1][j + 1] = mm[1];
-    out.p[2][j] = qq[0]; out.p[2][j + 1] = qq[1];
 }
 __device__ __forceinline__ void split8(const float* v, Parts& out) {
 #pragma unroll
@@ -289,22 +233,14 @@ __device__ __forceinline__ void transpose_inputs(const Parts (&f)[KB0], const bf
     }
 }
 
-// registers (2 j, 2 j + 1) of a fragment as one packed value
-__device__ __forceinline__ f32x2 pair_of(const f32x16& v, int j) { return f32x2{v[2 * j], v[2 * j + 1]}; }
-__device__ __forceinline__ void set_pair(f32x16& v, int j, f32x2 p) { v[2 * j] = p[0]; v[2 * j + 1] = p[1]; }
 // out = acc * (1 - h h), element-wise over a fragment (the tanh derivative through the activation itself)
 __device__ __forceinline__ void times_dtanh(const f32x16& acc, const f32x16& h, f32x16& out) {
-#if RL_SPLIT_PK
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const f32x2 hh = pair_of(h, j);
         const f32x2 d = __builtin_elementwise_fma(-hh, hh, f32x2{1.0f, 1.0f});
         set_pair(out, j, pair_of(acc, j) * d);
     }
-#else
-#pragma unroll
-    for (int r = 0; r < 16; ++r) out[r] = acc[r] * (1.0f - h[r] * h[r]);
-#endif
 }
 
 template <int DO, int DA, int WPS>
@@ -322,7 +258,7 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
     // weight -- its slot in x_ext is the constant 1): an LDS-direct piece costs the CU ~120 - 150 cycles whatever it carries
     // (profiles/r06_notes.md section 6; rounds 3 - 5 sent 8 KB0 + 1 pieces of 256 bytes here)
     constexpr int XPIECES = (DO + 1 + 7) / 8;
-    constexpr int XLAND_BYTES = RL_SPLIT_ASM_DMA ? XPIECES * WV * 16 : 0;
+    constexpr int XLAND_BYTES = XPIECES * WV * 16;
     constexpr int WAVE_BYTES = LAND_BYTES + SPILL_BYTES + XLAND_BYTES;
     constexpr int LDS_TOTAL = WAVES * WAVE_BYTES + (INV_LDS ? OPS_BYTES : 0) + (TAIL_LDS ? 2 * TAILV * 4 : 0);
     static_assert(DO + 1 <= 32, "two k-blocks of inputs + the bias slot");
@@ -343,7 +279,6 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
 
     // one tile ahead: the observation slots and the weight in registers, the cached activations by LDS-direct loads
     // (branch-free: a lane half beyond the inputs reads a clamped row and selects the constant)
-#if RL_SPLIT_ASM_DMA
     // The observations and the weight travel the same way as the activations, hidden from the compiler's wait-count
     // bookkeeping (a tracked load next to hidden ones would make every vmcnt(N) it computes wait for the younger hidden
     // loads too): lane L of piece p carries samples 4 (L & 7) .. + 3 of row 8 p + (L >> 3), so the piece lands row-major
@@ -369,28 +304,11 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
             }
         wq = xl[32 * DO];
     };
-#else
-    auto fetch = [&](int tile, float (&xq)[KB0][8], float& wq) {
-        const int b = tile * TS + lj;
-        wq = a.weight[b];
-#pragma unroll
-        for (int kb = 0; kb < KB0; ++kb)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int d = 16 * kb + 8 * lh + j;
-                const float v = a.obs[(size_t)(d < DO ? d : DO - 1) * B + b];
-                xq[kb][j] = d < DO ? v : (d == DO ? 1.0f : 0.0f);
-            }
-    };
-#endif
-#if RL_SPLIT_ASM_DMA
     // LDS byte address of this wavefront's landing zone (wave-uniform): M0 for rows 0..3, + 4096 for rows 4..7; the
     // instruction offset advances the global and the LDS address together (row q of a tile is 1 KB in both)
     const unsigned land_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)land);
-#endif
     auto fetch_acts = [&](int tile) {
         const float* src = a.acts + ((size_t)tile * 8 * WV + lane) * 4;
-#if RL_SPLIT_ASM_DMA
         asm volatile("s_mov_b32 m0, %2\n\t"
                      "global_load_lds_dwordx4 %0, off\n\t"
                      "global_load_lds_dwordx4 %0, off offset:1024\n\t"
@@ -402,11 +320,6 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
                      "global_load_lds_dwordx4 %1, off offset:2048\n\t"
                      "global_load_lds_dwordx4 %1, off offset:3072"
                      :: "v"(src), "v"(src + 4 * WV * 4), "s"(land_lds), "s"(land_lds + 4096u) : "memory");
-#else
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + q * WV * 4), (lptr_t)(land + q * WV * 16), 16, 0, 0);
-#endif
     };
     float xb[KB0][8], xb_next[KB0][8];
     float wgt = 0.0f, wgt_next = 0.0f;
@@ -537,13 +450,11 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
     for (int k = 0; k < DA; ++k) gb2[k] = 0.0f;
 
 
-#if RL_SPLIT_ASM_DMA
     // every load the compiler knows of (parameters, tangent, the staging above) has landed before the loop is entered,
     // and it is told so with an instruction it models: otherwise the loop header inherits "loads may be pending" from
     // the preheader and a vmcnt(N) wait for a loop-invariant value survives inside the loop, where it would wait for
     // the hidden loads of the next tile
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt / lgkmcnt untouched
-#endif
     for (int tile = wave_global; tile < n_tiles; tile += waves_total) {
         // ---- this tile's inputs; the next tile's start travelling ------------------------------------------------
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -555,15 +466,7 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { h0[4 * q + e] = v0[e]; h1[4 * q + e] = v1[e]; }
         }
-#if RL_SPLIT_ASM_DMA
         take_x(xb, wgt);
-#else
-#pragma unroll
-        for (int kb = 0; kb < KB0; ++kb)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) xb[kb][j] = xb_next[kb][j];
-        wgt = wgt_next;
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the landing zone is in registers before it is refilled
         {   // the wavefront's last tile prefetches itself again (no branch in the loop body)
             const int nxt = tile + waves_total < n_tiles ? tile + waves_total : tile;
@@ -584,13 +487,11 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
         auto stage = [&]() { if constexpr (TAIL_LDS) asm volatile("" ::: "memory"); };
 
         // ---- operands of this tile ---------------------------------------------------------------------------------------
-#if RL_SPLIT_OPS_AHEAD
         Parts opcur;
         if constexpr (INV_LDS) {              // the first operand block travels while the tile's inputs are split
             opcur = op(0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
         Parts Xs[KB0], H0s[2];
 #pragma unroll
         for (int kb = 0; kb < KB0; ++kb) split8(xb[kb], Xs[kb]);
@@ -600,41 +501,16 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#if RL_SPLIT_OPS_AHEAD
         if constexpr (INV_LDS) acc = chain_ahead(0, KB0, Xs, acc, opcur, KB0);    // dW0^T x + db0 (leaves block KB0 in opcur)
         else
-#endif
 #pragma unroll
         for (int kb = 0; kb < KB0; ++kb) acc = mm6(op(kb), Xs[kb], acc);          // dW0^T x + db0
         f32x16 dh0;
         times_dtanh(acc, h0, dh0);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = db1_(r);
-#if RL_SPLIT_OPS_AHEAD && RL_SPLIT_FILL
-        Parts D0s_f[2];
-        if constexpr (INV_LDS) {
-            // dW1^T h0 with the split of dh0 inside: per operand block one region of [three part reads of the next block,
-            // the split of eight values of dh0 twice, six products], the vector instructions spread between the products
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                Parts nxtp = op(kb == 0 ? KB0 + 1 : KB0 + 2);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 8; j += 2) split_pair_plain(dh0[8 * kb + j], dh0[8 * kb + j + 1], D0s_f[kb], j);
-                acc = mm6(opcur, H0s[kb], acc);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one matrix instruction
-                    __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);      // eight vector instructions
-                }
-                opcur = nxtp;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else
-#elif RL_SPLIT_OPS_AHEAD
         if constexpr (INV_LDS) acc = chain_ahead(KB0, 2, H0s, acc, opcur, KB0 + 2);     // dW1^T h0 (leaves W1^T's first block)
         else
-#endif
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) acc = mm6(op(KB0 + kb), H0s[kb], acc);       // dW1^T h0
         if constexpr (INV_LDS) {
@@ -646,15 +522,9 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
         stage();
         {
             Parts D0s[2];
-#if RL_SPLIT_OPS_AHEAD && RL_SPLIT_FILL
-            if constexpr (INV_LDS) { D0s[0] = D0s_f[0]; D0s[1] = D0s_f[1]; }
-            else
-#endif
             split_frag(dh0, D0s);
-#if RL_SPLIT_OPS_AHEAD
             if constexpr (INV_LDS) acc = chain_ahead(KB0 + 2, 2, D0s, acc, opcur, -1);  // W1^T dh0
             else
-#endif
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) acc = mm6(op(KB0 + 2 + kb), D0s[kb], acc);   // W1^T dh0
         }
@@ -663,7 +533,6 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
         f32x16 dz1;
         float gmu[DA];
         f32x16 gz1;
-#if RL_SPLIT_PK
         // the same sums with two fragment registers per instruction: the per-lane dot products of the output layer run
         // over register PAIRS (the two partial sums meet at the end), the outer-product and bias accumulators advance in pairs
 #pragma unroll
@@ -673,7 +542,6 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
             set_pair(dz1, j, d);
             set_pair(acc, j, pair_of(acc, j) * d);                                // dh1
         }
-#if RL_SPLIT_BULK_ROWS
         // rows r = 0 .. 15 of column k (which: 0 = W2, 1 = its tangent) of this lane half: four 16-byte reads (LDS) or moves
         auto rows_of = [&](int which, int k, f32x4 (&out_)[4]) {
 #pragma unroll
@@ -733,91 +601,17 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
                 gb1l[2 * j] = b1n[0]; gb1l[2 * j + 1] = b1n[1];
             }
         }
-#else
-#pragma unroll
-        for (int k = 0; k < DA; ++k) {
-            f32x2 pd = {0.0f, 0.0f};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                pd = __builtin_elementwise_fma(pair_of(h1, j), f32x2{dW2_(2 * j, k), dW2_(2 * j + 1, k)}, pd);
-                pd = __builtin_elementwise_fma(pair_of(acc, j), f32x2{W2_(2 * j, k), W2_(2 * j + 1, k)}, pd);
-            }
-            const float dmu = db2[k] + half_sum_swap(pd[0] + pd[1]);
-            gmu[k] = c * dmu * fk[k];
-        }
-        if (lh == 0) {
-            wsum += c;
-#pragma unroll
-            for (int k = 0; k < DA; ++k) gb2[k] += gmu[k];
-        }
-        // ---- back-propagation, sample-major ---------------------------------------------------------------------------------
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            f32x2 g = {0.0f, 0.0f};
-#pragma unroll
-            for (int k = 0; k < DA; ++k) {
-                const f32x2 gk = {gmu[k], gmu[k]};
-                g = __builtin_elementwise_fma(f32x2{W2_(2 * j, k), W2_(2 * j + 1, k)}, gk, g);
-                const f32x2 w2 = __builtin_elementwise_fma(pair_of(h1, j), gk, f32x2{gW2l[2 * j][k], gW2l[2 * j + 1][k]});
-                gW2l[2 * j][k] = w2[0]; gW2l[2 * j + 1][k] = w2[1];
-            }
-            const f32x2 gz = g * pair_of(dz1, j);
-            set_pair(gz1, j, gz);
-            const f32x2 b1n = f32x2{gb1l[2 * j], gb1l[2 * j + 1]} + gz;
-            gb1l[2 * j] = b1n[0]; gb1l[2 * j + 1] = b1n[1];
-        }
-#endif
-#else
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            dz1[r] = 1.0f - h1[r] * h1[r];
-            acc[r] *= dz1[r];                                                     // dh1
-        }
-#pragma unroll
-        for (int k = 0; k < DA; ++k) {
-            float pd = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                pd = __builtin_fmaf(h1[r], dW2_(r, k), pd);
-                pd = __builtin_fmaf(acc[r], W2_(r, k), pd);
-            }
-            const float dmu = db2[k] + half_sum_swap(pd);
-            gmu[k] = c * dmu * fk[k];
-        }
-        if (lh == 0) {
-            wsum += c;
-#pragma unroll
-            for (int k = 0; k < DA; ++k) gb2[k] += gmu[k];
-        }
-
-        // ---- back-propagation, sample-major ---------------------------------------------------------------------------------
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float g = 0.0f;
-#pragma unroll
-            for (int k = 0; k < DA; ++k) {
-                g = __builtin_fmaf(W2_(r, k), gmu[k], g);
-                gW2l[r][k] = __builtin_fmaf(h1[r], gmu[k], gW2l[r][k]);
-            }
-            gz1[r] = g * dz1[r];
-            gb1l[r] += gz1[r];
-        }
-#endif
         stage();
-#if RL_SPLIT_OPS_AHEAD
         if constexpr (INV_LDS) {
             opcur = op(KB0 + 4);
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
         Parts G1s[2];
         split_frag(gz1, G1s);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#if RL_SPLIT_OPS_AHEAD
         if constexpr (INV_LDS) acc = chain_ahead(KB0 + 4, 2, G1s, acc, opcur, -1);      // W1 gz1
         else
-#endif
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) acc = mm6(op(KB0 + 4 + kb), G1s[kb], acc);       // W1 gz1
         stage();
@@ -896,20 +690,11 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_split_kernel(Args a) {
 #pragma unroll
         for (int k = 0; k < DA; ++k) {
             myrow[N::B2 + k] = b2s[k];
-            // log_std block of the Fisher: d2KL/ds2 = 4 v (2 v - eps) / (2 v + eps)^2, v = sigma^2
-            const float vv = var_[k], e = 1e-8f;
-            const float cc = floored[k] ? 0.0f : 4.0f * vv * (2.0f * vv - e) / ((2.0f * vv + e) * (2.0f * vv + e));
-            myrow[N::LSTD + k] = cc * vc[N::LSTD + k] * ws;
+            myrow[N::LSTD + k] = log_std_fisher(var_[k], floored[k]) * vc[N::LSTD + k] * ws;
         }
     }
     __syncthreads();
-    float* row = a.partial + (size_t)blockIdx.x * P;
-    for (int k = threadIdx.x; k < P; k += WAVES * WV) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) t += reinterpret_cast<const float*>(smem)[w * P + k];
-        row[k] = t;
-    }
+    fold_rows<WAVES, P>(smem, a.partial);
 }
 
 // =====================================================================================================================
@@ -1354,80 +1139,32 @@ __global__ void __launch_bounds__(4 * WV, 1) fvp_split64_kernel(Args a) {
 #pragma unroll
         for (int k = 0; k < DA; ++k) {
             myrow[N::B2 + k] = b2s[k];
-            const float vv = var_[k], e = 1e-8f;
-            const float cc = floored[k] ? 0.0f : 4.0f * vv * (2.0f * vv - e) / ((2.0f * vv + e) * (2.0f * vv + e));
-            myrow[N::LSTD + k] = cc * vc[N::LSTD + k] * ws;
+            myrow[N::LSTD + k] = log_std_fisher(var_[k], floored[k]) * vc[N::LSTD + k] * ws;
         }
     }
     __syncthreads();
-    float* row = a.partial + (size_t)blockIdx.x * P;
-    for (int k = threadIdx.x; k < P; k += WAVES * WV) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) t += reinterpret_cast<const float*>(smem)[w * P + k];
-        row[k] = t;
-    }
+    fold_rows<WAVES, P>(smem, a.partial);
 }
 
 template <int DO, int DA>
 static int launch64(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st) {
-    using N = Net<DO, DA, 64>;
-    constexpr int HT = 2, WAVES = 4;
+    constexpr int HT = 2, WAVES = 4;               // one wavefront per SIMD
     constexpr int KB0 = (DO + 1 + 15) / 16;
     constexpr int N_OPS = HT * KB0 + 3 * HT * 2 * HT;
     constexpr int LDS_BYTES = WAVES * (2 * 64 * TS * 4 + TS * 8 * 4) + N_OPS * 3 * WV * 16 + 2 * (HT * 16 * DA * 2 + HT * 16) * 4;
-    Args a;
-    a.B = g->n_samples; a.theta = g->theta; a.vec = vec; a.acts = g->activations; a.obs = g->obs; a.weight = g->weights;
-    a.inv_count = g->inv_count; a.log_min_std = g->log_min_std;
-    const int n_tiles = a.B / TS;
-    int grid = (n_tiles + WAVES - 1) / WAVES;
-    if (grid > 256) grid = 256;                   // one workgroup per CU, one wavefront per SIMD
-    const size_t need = (size_t)grid * N::P * sizeof(float);
-    if (ws_bytes < need) return set_error(RL_ERR_ARG, "policy pass workspace too small: %zu < %zu bytes", ws_bytes, need);
-    a.partial = (float*)ws;
-    auto kern = fvp_split64_kernel<DO, DA>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           LDS_BYTES);
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * WV), LDS_BYTES, st, a);
-    int rc = check_launch("fvp_split64_kernel");
-    if (rc) return rc;
-    return launch_reduce_rows(a.partial, grid, N::P, out, st);
+    return launch_tiles<fvp_split64_kernel<DO, DA>, WAVES, TS, LDS_BYTES, Net<DO, DA, 64>::P>("fvp_split64_kernel", make_args<Args>(g, vec),
+                                                                                            ws, ws_bytes, out, st);
 }
 
 template <int DO, int DA, int WPS>
 static int launch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st) {
-    using N = Net<DO, DA, H>;
     constexpr int WAVES = 4 * WPS;
     constexpr int KB0 = (DO + 1 + 15) / 16;
-    constexpr int LDS_BYTES = WAVES * (LAND_BYTES + (WPS == 2 ? 2 * 3 * WV * 16 : 0) + (RL_SPLIT_ASM_DMA ? ((DO + 1 + 7) / 8) * WV * 16 : 0)) +
+    constexpr int LDS_BYTES = WAVES * (LAND_BYTES + (WPS == 2 ? 2 * 3 * WV * 16 : 0) + ((DO + 1 + 7) / 8) * WV * 16) +
                               (WPS == 2 ? ops_bytes(KB0) : 0) +
                               ((WPS == 2 || DA > 2) ? 2 * (16 * DA * 2 + 16) * 4 : 0);
-    Args a;
-    a.B = g->n_samples; a.theta = g->theta; a.vec = vec; a.acts = g->activations; a.obs = g->obs; a.weight = g->weights;
-    a.inv_count = g->inv_count; a.log_min_std = g->log_min_std;
-    const int n_tiles = a.B / TS;
-    int grid = (n_tiles + WAVES - 1) / WAVES;
-    if (grid > 256) grid = 256;                   // one workgroup per CU
-    const size_t need = (size_t)grid * N::P * sizeof(float);
-    if (ws_bytes < need) return set_error(RL_ERR_ARG, "policy pass workspace too small: %zu < %zu bytes", ws_bytes, need);
-    a.partial = (float*)ws;
-    auto kern = fvp_split_kernel<DO, DA, WPS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           LDS_BYTES);
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * WV), LDS_BYTES, st, a);
-    int rc = check_launch("fvp_split_kernel");
-    if (rc) return rc;
-    return launch_reduce_rows(a.partial, grid, N::P, out, st);
+    return launch_tiles<fvp_split_kernel<DO, DA, WPS>, WAVES, TS, LDS_BYTES, Net<DO, DA, H>::P>("fvp_split_kernel", make_args<Args>(g, vec),
+                                                                                              ws, ws_bytes, out, st);
 }
 
 }  // namespace split
@@ -1435,12 +1172,6 @@ static int launch(const rl_policy_batch* g, const float* vec, void* ws, size_t w
 // The split product takes a cached Fisher-vector product of a two-layer 32-unit tanh net whose batch is a whole number
 // of tiles; everything else stays on policy_pass_kernel.  rl_launch_opts.fvp_split = 1 switches it off (A/B runs, tests of
 // the bit-identical cached / recomputed pair).  Returns RL_SPLIT_NOT_TAKEN when the launch is not its to make.
-// (obs_dim, act_dim) of the HIP-native envs (a (32, 32) net is rllab's default policy for every one of them) + the
-// one-output net on the Swimmer's observations.  Heads wider than two outputs run one wavefront per SIMD: their
-// per-lane sums of the thin products (16 x act_dim registers) do not fit beside 256.
-#define SPLIT_SHAPES(X) X(4, 1) X(6, 1) X(11, 1) X(13, 2) X(13, 1) X(20, 3) X(20, 6) X(21, 6)
-// ... and two 64-unit layers (fvp_split64_kernel): the pairs policy_pass_kernel<Net<.., 64>> caches activations for
-#define SPLIT64_SHAPES(X) X(4, 1) X(6, 1) X(11, 1) X(13, 2) X(20, 3) X(20, 6) X(21, 6)
 bool split_fvp_takes(const rl_policy_batch* g) {
     if (!g->activations || g->hidden2 != 0 || g->hidden0 != g->hidden1 || (g->hidden0 != 32 && g->hidden0 != 64) ||
         g->activation != RL_ACT_TANH || g->layer_activations != 0 || g->n_samples <= 0 || g->n_samples % TS != 0)
@@ -1459,12 +1190,8 @@ bool split_fvp_takes(const rl_policy_batch* g) {
 #undef SPLITCASE
     return false;
 }
-bool split16_fvp_takes(const rl_policy_batch* g);                       // policy_split16_kernels.hip
-int split16_fvp_dispatch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st);
 int split_fvp_dispatch(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st) {
     if (!split_fvp_takes(g)) return RL_SPLIT_NOT_TAKEN;
-    // rl_launch_opts.fvp_split = 3: the 16-sample-tile kernel, four wavefronts per SIMD, for the shapes it is built for (A/B)
-    if (g->opts && g->opts->fvp_split == 3 && split16_fvp_takes(g)) return split16_fvp_dispatch(g, vec, ws, ws_bytes, out, st);
     // two wavefronts per SIMD (operands in LDS) unless rl_launch_opts.fvp_split_wps = 1 asks for the one-wavefront, register-resident form
     if (g->hidden0 == 64) {
 #define SPLITCASE(DO, DA) if (g->obs_dim == DO && g->act_dim == DA) return split::launch64<DO, DA>(g, vec, ws, ws_bytes, out, st);
@@ -1482,15 +1209,3 @@ int split_fvp_dispatch(const rl_policy_batch* g, const float* vec, void* ws, siz
 }
 
 }  // namespace rl
-
-namespace rl { bool csplit_fvp_takes(const rl_policy_batch* g); }     // policy_csplit_kernels.hip
-namespace rl { bool split16_fvp_takes(const rl_policy_batch* g); }    // policy_split16_kernels.hip
-namespace rl { bool splith_fvp_takes(const rl_policy_batch* g); }     // policy_splith_kernels.hip
-
-extern "C" int rl_policy_fvp_variant(const rl_policy_batch* g) {
-    if (!g) return rl::set_error(RL_ERR_ARG, "rl_policy_fvp_variant: null batch");
-    if (g->opts && g->opts->fvp_split == 3 && rl::split_fvp_takes(g) && rl::split16_fvp_takes(g)) return 3;
-    if (rl::splith_fvp_takes(g)) return 4;
-    if (rl::split_fvp_takes(g)) return 1;
-    return rl::csplit_fvp_takes(g) ? 2 : 0;
-}

@@ -7,8 +7,7 @@
 //   per-tile operand b:      hi = f16(b),  lo' = f16(2^11 (b - hi))          b = hi + 2^-11 lo' to ~2^-23 |b|, |b| in [2^-13, 2^15]
 //   loop-invariant image A:  hi = f16(A),  lo = f16(A - hi),  hs = f16(2^-11 hi)   (A scaled by a power of two to sit high)
 //   A b  = A.hi b.hi + A.lo b.hi + A.hs b.lo'                                 one f32 accumulator, three instructions
-//   a^T b over samples (both per tile):  c0 += a.hi b.hi,  c1 += a.hi b.lo' + a.lo' b.hi,  result c0 + 2^-11 c1
-//                                        or (H = 64: registers) a as an image: lo = 2^-11 lo', hs = 2^-11 hi
+//   a^T b over samples (both per tile):  a as an image, lo = 2^-11 lo', hs = 2^-11 hi  (a is h0 or x~: magnitudes known)
 // The matrix pipe honours f16 subnormal inputs and, measured against float64 over ten magnitude regimes, this product is
 // closer than an f32 fma chain (9e-8 against 1.0e-7 normwise; the bf16 six-term form 6.9e-8; tools/ubench/f16_split.hip,
 // profiles/r06_f16_split.txt).  What f16 lacks is RANGE, so every operand class carries a power-of-two scale chosen per launch from
@@ -22,14 +21,10 @@
 // (tests/test_gpu_fvp_split.py runs every test of the bf16 kernels on these too).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "../../include/rllab_amd.h"
-#include "capi_util.h"
-#include "policy_mfma.h"
+#include "fvp_split_common.h"
 #include "lds_tr_image.h"
 
 namespace rl {
-
-int launch_reduce_rows(const float* partial, int rows, int cols, double* out, hipStream_t st);   // policy_kernels.hip
 
 namespace splith {
 
@@ -37,8 +32,6 @@ typedef _Float16 f16;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -87,12 +80,6 @@ __device__ __forceinline__ f32x16 mm_ab(const PA& A, const PB& b, f32x16 c) {
     c = mf(A.hi, b.hi, c);
     return c;
 }
-// both operands per tile: c0 += a.hi b.hi, c1 += the cross terms (result c0 + 2^-11 c1)
-__device__ __forceinline__ void mm_bb(const PB& a, const PB& b, f32x16& c0, f32x16& c1) {
-    c1 = mf(a.hi, b.lo, c1);
-    c1 = mf(a.lo, b.hi, c1);
-    c0 = mf(a.hi, b.hi, c0);
-}
 // a per-tile operand of known good magnitude as an image (exact wherever the scaled part stays a normal number)
 __device__ __forceinline__ PA as_image(const PB& a) {
     const f16 k = (f16)0.00048828125f;      // 2^-11
@@ -101,20 +88,12 @@ __device__ __forceinline__ PA as_image(const PB& a) {
     return r;
 }
 
-__device__ __forceinline__ float half_sum_swap(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// b = hi + 2^-11 lo'.  RL_SPLITH_MIX: five instructions per pair -- v_cvt_pk_f16_f32, the residuals as two v_fma_mix_f32
+// b = hi + 2^-11 lo'.  Five instructions per pair -- v_cvt_pk_f16_f32, the residuals as two v_fma_mix_f32
 // (f16 half x -1 + f32, exact), the scaled parts as v_fma_mixlo_f16 / v_fma_mixhi_f16 (f32 x 2^11 rounded to f16 once) --
 // where the compiler's own selection is seven (two unpacking conversions, two packed f32 operations, a packed conversion);
-// tools/ubench/f16_split.hip checks the two forms bit for bit on the device.
-#ifndef RL_SPLITH_MIX
-#define RL_SPLITH_MIX 1
-#endif
+// tools/ubench/f16_split.hip checks the two forms bit for bit on the device (once the build-time switch RL_SPLITH_MIX; the
+// compiler's form is gone).
 __device__ __forceinline__ void split_pair(float a0, float a1, PB& out, int j) {
-#if RL_SPLITH_MIX
 #if RL_ABL_SPLIT
     unsigned hb, lb;
     asm volatile("" : "=v"(hb), "=v"(lb) : "v"(a0), "v"(a1));
@@ -131,11 +110,6 @@ __device__ __forceinline__ void split_pair(float a0, float a1, PB& out, int j) {
         : "=&v"(hb), "=&v"(lb), "=&v"(r0), "=&v"(r1) : "v"(a0), "v"(a1), "s"(k));
 #endif
     const f16x2 h = __builtin_bit_cast(f16x2, hb), l = __builtin_bit_cast(f16x2, lb);
-#else
-    const f16x2 h = __builtin_convertvector(f32x2{a0, a1}, f16x2);
-    const float r0 = a0 - (float)h[0], r1 = a1 - (float)h[1];                                                // exact
-    const f16x2 l = __builtin_convertvector(f32x2{r0, r1} * f32x2{2048.0f, 2048.0f}, f16x2);
-#endif
     out.hi[j] = h[0]; out.hi[j + 1] = h[1];
     out.lo[j] = l[0]; out.lo[j + 1] = l[1];
 }
@@ -143,7 +117,7 @@ __device__ __forceinline__ void split_pair(float a0, float a1, PB& out, int j) {
 // statements (59 per tile in the first build), and a stage's instructions are issued stage by stage so that no instruction
 // waits on the one in front of it
 __device__ __forceinline__ void split8v(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7, PB& out) {
-#if RL_SPLITH_MIX && !RL_ABL_SPLIT
+#if !RL_ABL_SPLIT
     unsigned h0, h1, h2, h3, l0, l1, l2, l3;
     float r0, r1, r2, r3, r4, r5, r6, r7;
     const float k = 2048.0f;
@@ -271,8 +245,6 @@ __device__ __forceinline__ void transpose_inputs(const PB (&f)[KB0], const f16x8
     pack_exact(d, out[0].lo, out[1].lo);
 }
 
-__device__ __forceinline__ f32x2 pair_of(const f32x16& v, int j) { return f32x2{v[2 * j], v[2 * j + 1]}; }
-__device__ __forceinline__ void set_pair(f32x16& v, int j, f32x2 p) { v[2 * j] = p[0]; v[2 * j + 1] = p[1]; }
 // out = acc * (1 - h h) * k
 __device__ __forceinline__ void times_dtanh(const f32x16& acc, const f32x16& h, f32x16& out, float k = 1.0f) {
 #pragma unroll
@@ -383,12 +355,9 @@ constexpr int H = 32;
 constexpr int LAND_BYTES = 2 * H * TS * 4;
 constexpr int ops_count(int kb0) { return kb0 + 6; }
 constexpr int ops_bytes(int kb0) { return ops_count(kb0) * 3 * WV * 16; }
-#ifndef RL_SPLITH_TWO_ACC
-#define RL_SPLITH_TWO_ACC 0      // gW1 += h0^T gz1~: two accumulators (1: 47 spilled registers with both) or h0 as an image (0)
-#endif
-#ifndef RL_SPLITH_TWO_ACC_W0
-#define RL_SPLITH_TWO_ACC_W0 0   // gW0 += x~^T gz0~: two accumulators (1: 31 spilled registers) or x~ as an image (0)
-#endif
+// The two sample-contracted products take their sample-side operand as an IMAGE (below).  The alternative, once the build-time
+// switches RL_SPLITH_TWO_ACC (gW1 += h0^T gz1~) and RL_SPLITH_TWO_ACC_W0 (gW0 += x~^T gz0~), was two accumulators per product
+// (c0 + 2^-11 c1): 47 spilled registers with both, 31 with the second alone.
 // The sample-side operand as an image multiplies its parts by 2^-11, which must not push them into the f16 subnormals:
 // h0 lives in (-1, 1) (exact from 2^-3 up, an absolute 2^-25 below), and the observations are transposed with 2^8 x identity
 // (XT_SCALE; x~ < 2^6, so 2^8 x~ < 2^14): an observation down to 2^-17 of the batch maximum keeps every bit.
@@ -544,6 +513,8 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
         for (int kb = 0; kb < KB0; ++kb) Idx[kb][j] = (f16)(16 * kb + 8 * lh + j == lj ? XT_SCALE : 0.0f);
 
     // ---- accumulators ---------------------------------------------------------------------------------------------
+    // (gW1c / gW0c: the cross-term accumulators of the retired two-accumulator form.  Nothing adds to them any more, but the
+    // fold's fma with them is an instruction of the pinned stream -- x + 0 is not x for x = -0 -- so they go in a change of their own)
     f32x16 gW1, gW0, gW1c, gW0c;
     float gW2l[16][DA], gb1l[16], gb2[DA], wsum = 0.0f;
 #pragma unroll
@@ -711,20 +682,12 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {                              // gW1 += h0^T gz1~ (samples are K)
-#if RL_SPLITH_TWO_ACC
-                mm_bb(H0t[kb], G1t[kb], gW1, gW1c);
-#else
                 gW1 = mm_ab(as_image(H0t[kb]), G1t[kb], gW1);
-#endif
             }
             transpose_inputs<KB0>(Xs, Idx, Xt);
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {                              // gW0 += x~_ext^T gz0~
-#if RL_SPLITH_TWO_ACC_W0
-                mm_bb(Xt[kb], G0t[kb], gW0, gW0c);
-#else
                 gW0 = mm_ab(as_image(Xt[kb]), G0t[kb], gW0);
-#endif
             }
         }
     }
@@ -774,19 +737,11 @@ __global__ void __launch_bounds__(4 * WPS * WV, 1) fvp_splith_kernel(Args a) {
 #pragma unroll
         for (int k = 0; k < DA; ++k) {
             myrow[N::B2 + k] = b2s[k] * S.u1;
-            const float vv = var_[k], e = 1e-8f;
-            const float cc = floored[k] ? 0.0f : 4.0f * vv * (2.0f * vv - e) / ((2.0f * vv + e) * (2.0f * vv + e));
-            myrow[N::LSTD + k] = cc * vc[N::LSTD + k] * ws;
+            myrow[N::LSTD + k] = log_std_fisher(var_[k], floored[k]) * vc[N::LSTD + k] * ws;
         }
     }
     __syncthreads();
-    float* row = a.partial + (size_t)blockIdx.x * P;
-    for (int k = threadIdx.x; k < P; k += WAVES * WV) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) t += reinterpret_cast<const float*>(smem)[w * P + k];
-        row[k] = t;
-    }
+    fold_rows<WAVES, P>(smem, a.partial);
 }
 
 // =====================================================================================================================
@@ -1199,93 +1154,44 @@ __global__ void __launch_bounds__(4 * WV, 1) fvp_splith64_kernel(Args a) {
 #pragma unroll
         for (int k = 0; k < DA; ++k) {
             myrow[N::B2 + k] = b2s[k] * S.u1;
-            const float vv = var_[k], e = 1e-8f;
-            const float cc = floored[k] ? 0.0f : 4.0f * vv * (2.0f * vv - e) / ((2.0f * vv + e) * (2.0f * vv + e));
-            myrow[N::LSTD + k] = cc * vc[N::LSTD + k] * ws;
+            myrow[N::LSTD + k] = log_std_fisher(var_[k], floored[k]) * vc[N::LSTD + k] * ws;
         }
     }
     __syncthreads();
-    float* row = a.partial + (size_t)blockIdx.x * P;
-    for (int k = threadIdx.x; k < P; k += WAVES * WV) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) t += reinterpret_cast<const float*>(smem)[w * P + k];
-        row[k] = t;
-    }
+    fold_rows<WAVES, P>(smem, a.partial);
 }
 
-static Args make_args(const rl_policy_batch* g, const float* vec) {
-    Args a;
-    a.B = g->n_samples; a.theta = g->theta; a.vec = vec; a.acts = g->activations; a.obs = g->obs; a.weight = g->weights;
-    a.xmax = g->obs_absmax; a.inv_count = g->inv_count; a.log_min_std = g->log_min_std; a.partial = nullptr;
+static Args make_args_h(const rl_policy_batch* g, const float* vec) {
+    Args a = make_args<Args>(g, vec);
+    a.xmax = g->obs_absmax;
     return a;
 }
 
 template <int DO, int DA>
 static int launch32(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st) {
-    using N = Net<DO, DA, H>;
     constexpr int WPS = DA <= 2 ? 2 : 1;
     constexpr int WAVES = 4 * WPS;
     constexpr int KB0 = (DO + 1 + 15) / 16;
     constexpr int LDS_BYTES = WAVES * (LAND_BYTES + 2 * 2 * WV * 16 + ((DO + 1 + 7) / 8) * WV * 16) + ops_bytes(KB0) +
                               2 * (16 * DA * 2 + 16) * 4 + WAVES * 5 * 4;
-    Args a = make_args(g, vec);
-    const int n_tiles = a.B / TS;
-    int grid = (n_tiles + WAVES - 1) / WAVES;
-    if (grid > 256) grid = 256;                   // one workgroup per CU
-    const size_t need = (size_t)grid * N::P * sizeof(float);
-    if (ws_bytes < need) return set_error(RL_ERR_ARG, "policy pass workspace too small: %zu < %zu bytes", ws_bytes, need);
-    a.partial = (float*)ws;
-    auto kern = fvp_splith_kernel<DO, DA, WPS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           LDS_BYTES);
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * WV), LDS_BYTES, st, a);
-    int rc = check_launch("fvp_splith_kernel");
-    if (rc) return rc;
-    return launch_reduce_rows(a.partial, grid, N::P, out, st);
+    return launch_tiles<fvp_splith_kernel<DO, DA, WPS>, WAVES, TS, LDS_BYTES, Net<DO, DA, H>::P>("fvp_splith_kernel", make_args_h(g, vec),
+                                                                                               ws, ws_bytes, out, st);
 }
 
 template <int DO, int DA>
 static int launch64(const rl_policy_batch* g, const float* vec, void* ws, size_t ws_bytes, double* out, hipStream_t st) {
-    using N = Net<DO, DA, 64>;
-    constexpr int HT = 2, WAVES = 4;
+    constexpr int HT = 2, WAVES = 4;               // one wavefront per SIMD
     constexpr int KB0 = (DO + 1 + 15) / 16;
     constexpr int N_OPS = HT * KB0 + 3 * HT * 2 * HT;
     constexpr int LDS_BYTES = WAVES * (2 * 64 * TS * 4 + TS * 8 * 4) + N_OPS * 3 * WV * 16 + 2 * (HT * 16 * DA * 2 + HT * 16) * 4 +
                               WAVES * 5 * 4;
-    Args a = make_args(g, vec);
-    const int n_tiles = a.B / TS;
-    int grid = (n_tiles + WAVES - 1) / WAVES;
-    if (grid > 256) grid = 256;                   // one workgroup per CU, one wavefront per SIMD
-    const size_t need = (size_t)grid * N::P * sizeof(float);
-    if (ws_bytes < need) return set_error(RL_ERR_ARG, "policy pass workspace too small: %zu < %zu bytes", ws_bytes, need);
-    a.partial = (float*)ws;
-    auto kern = fvp_splith64_kernel<DO, DA>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           LDS_BYTES);
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * WV), LDS_BYTES, st, a);
-    int rc = check_launch("fvp_splith64_kernel");
-    if (rc) return rc;
-    return launch_reduce_rows(a.partial, grid, N::P, out, st);
+    return launch_tiles<fvp_splith64_kernel<DO, DA>, WAVES, TS, LDS_BYTES, Net<DO, DA, 64>::P>("fvp_splith64_kernel", make_args_h(g, vec),
+                                                                                             ws, ws_bytes, out, st);
 }
 
 }  // namespace splith
 
-// the (obs_dim, act_dim) pairs of fvp_split_kernel and of fvp_split64_kernel
-#define SPLITH_SHAPES(X) X(4, 1) X(6, 1) X(11, 1) X(13, 2) X(13, 1) X(20, 3) X(20, 6) X(21, 6)
-#define SPLITH64_SHAPES(X) X(4, 1) X(6, 1) X(11, 1) X(13, 2) X(20, 3) X(20, 6) X(21, 6)
-bool split_fvp_takes(const rl_policy_batch* g);                          // policy_split_kernels.hip
-// The f16 form takes what the bf16 split kernels take, for the shapes above, when the caller provides max |obs|
+// The f16 form takes what the bf16 split kernels take (SPLIT_SHAPES / SPLIT64_SHAPES), when the caller provides max |obs|
 // (rl_policy_batch.obs_absmax) and does not ask for another kernel (rl_launch_opts.fvp_split: 0 = the library's choice,
 // 4 = this one).
 bool splith_fvp_takes(const rl_policy_batch* g) {
@@ -1294,8 +1200,8 @@ bool splith_fvp_takes(const rl_policy_batch* g) {
     if (req != 0 && req != 4) return false;
     if (g->opts && g->opts->fvp_split_wps == 1) return false;
 #define SPLITCASE(DO, DA) if (g->obs_dim == DO && g->act_dim == DA) return true;
-    if (g->hidden0 == 64) { SPLITH64_SHAPES(SPLITCASE) }
-    else { SPLITH_SHAPES(SPLITCASE) }
+    if (g->hidden0 == 64) { SPLIT64_SHAPES(SPLITCASE) }
+    else { SPLIT_SHAPES(SPLITCASE) }
 #undef SPLITCASE
     return false;
 }
@@ -1303,12 +1209,12 @@ int splith_fvp_dispatch(const rl_policy_batch* g, const float* vec, void* ws, si
     if (!splith_fvp_takes(g)) return RL_SPLIT_NOT_TAKEN;
     if (g->hidden0 == 64) {
 #define SPLITCASE(DO, DA) if (g->obs_dim == DO && g->act_dim == DA) return splith::launch64<DO, DA>(g, vec, ws, ws_bytes, out, st);
-        SPLITH64_SHAPES(SPLITCASE)
+        SPLIT64_SHAPES(SPLITCASE)
 #undef SPLITCASE
         return RL_SPLIT_NOT_TAKEN;
     }
 #define SPLITCASE(DO, DA) if (g->obs_dim == DO && g->act_dim == DA) return splith::launch32<DO, DA>(g, vec, ws, ws_bytes, out, st);
-    SPLITH_SHAPES(SPLITCASE)
+    SPLIT_SHAPES(SPLITCASE)
 #undef SPLITCASE
     return RL_SPLIT_NOT_TAKEN;
 }

@@ -28,20 +28,16 @@
 // 32-sample tile (forward 284 + tangent 540 + back-propagation 256 + outer products 272 + input layer), 350 per
 // wavefront; HBM sees 4 (DO + 1) bytes per sample per pass.
 #include <hip/hip_runtime.h>
-#include "../../include/rllab_amd.h"
-#include "capi_util.h"
-#include "policy_mfma.h"
+#include "fvp_split_common.h"      // launch_reduce_rows
 #include "policy_wide.h"
 
 namespace rl {
 
-int launch_reduce_rows(const float* partial, int rows, int cols, double* out, hipStream_t st);   // policy_kernels.hip
 int launch_reduce_loss(const double* partial, int rows, double* out, hipStream_t st);
 
 #ifndef WIDE_PREFETCH
 #define WIDE_PREFETCH 1
 #endif
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int WW = 4;                  // wavefronts per workgroup = row tiles of the widest layer
 constexpr int WNT = WW * WV;
 constexpr int BS = WIDE_BS;
@@ -965,13 +961,8 @@ static int launch_wide(const WideShape& s, const rl_policy_batch* g, const float
     int rc = check_launch("wide_stage_kernel");
     if (rc) return rc;
     auto kern = wide_pass_kernel<L, MODE, KSPLIT, MT, MD>;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return set_error(RL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_lds = 160 * 1024;
-    }
+    static bool attr_set = false;
+    if ((rc = allow_dynamic_lds(kern, 160 * 1024, attr_set))) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WNT), lds, st, a);
     rc = check_launch("wide_pass_kernel");
     if (rc) return rc;

@@ -100,6 +100,33 @@ def test_every_switch_is_a_field_of_the_options_struct(clean_env):
     assert all(getattr(o, f) == 0 for f, _ in _lib.LaunchOpts._fields_[:-1])
 
 
+def test_reserved_words_must_be_zero(clean_env):
+    """rl_launch_opts.reserved[] steers nothing (the timing ablation of fvp_split16_kernel that once hung on reserved[0] is
+    a build-time switch): the entry points that read the struct refuse a non-zero word and name it, and launch_opts leaves
+    them 0 whatever RLLAB_SPLIT16_ABLATE says."""
+    import ctypes
+    from rllab_amd import _lib
+    ERR_ARG = -1                                     # RL_ERR_ARG (include/rllab_amd.h)
+    opts = _lib.LaunchOpts()
+    b = _lib.PolicyBatch(n_samples=64, obs_dim=13, act_dim=2, hidden0=32, hidden1=32, activation=_lib.ACT_TANH,
+                         activations=256, obs_absmax=256, opts=ctypes.addressof(opts))      # (read for being set only)
+    a = _lib.RolloutArgs(kind=_lib.ENV_CARTPOLE, n_envs=4096, horizon=100, hidden0=32, hidden1=32, opts=ctypes.addressof(opts))
+    plan = _lib.RolloutPlan()
+    assert _lib.lib.rl_policy_fvp_variant(ctypes.byref(b)) == 4
+    assert _lib.lib.rl_rollout_plan_query(ctypes.byref(a), ctypes.byref(plan)) == 0 and plan.kernel == 1
+    for word in (0, 6):
+        opts.reserved[word] = 1
+        assert _lib.lib.rl_policy_fvp_variant(ctypes.byref(b)) == ERR_ARG
+        assert "reserved[%d]" % word in _lib.lib.rl_last_error().decode()
+        assert _lib.lib.rl_rollout_plan_query(ctypes.byref(a), ctypes.byref(plan)) == ERR_ARG
+        assert "reserved[%d]" % word in _lib.lib.rl_last_error().decode()
+        opts.reserved[word] = 0
+    clean_env.setenv("RLLAB_SPLIT16_ABLATE", "3")
+    o = ctypes.cast(_lib.launch_opts(), ctypes.POINTER(_lib.LaunchOpts)).contents
+    assert list(o.reserved) == [0] * 7
+    test_every_switch_is_a_field_of_the_options_struct(clean_env)
+
+
 def test_header_documents_every_field():
     text = open(os.path.join(ROOT, "include", "rllab_amd.h")).read()
     body = text[text.index("typedef struct rl_launch_opts {"):text.index("} rl_launch_opts;")]

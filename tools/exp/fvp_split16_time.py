@@ -1,6 +1,13 @@
 #!/usr/bin/env python
 """fvp_split_kernel (two wavefronts per SIMD, 32-sample tiles) against fvp_split16_kernel (RLLAB_FVP_SPLIT=3: four per
-SIMD, 16-sample tiles), interleaved in one process, at the headline batch.  GPU box."""
+SIMD, 16-sample tiles), interleaved in one process, at the headline batch.  GPU box.
+
+  python tools/exp/fvp_split16_time.py [n_shapes [ablation]]
+
+The timing ablations of fvp_split16_kernel (the tile loop re-uses the first tile's inputs: WRONG results) are a build-time
+switch of csrc/policy_split16_kernels.hip, like every RL_ABL_* one: build the library with -DRL_ABL_SPLIT16_FETCH=1 (no fetch of
+the cached fragments), 2 (none of the observations / weight) or 3 (neither) and name that value as ``ablation``; the split16
+rows are then tagged with it.  This script cannot tell which build it runs."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -23,12 +30,10 @@ for do, da, B in [(13, 2, 2048000), (4, 1, 409600), (13, 2, 8192000)][:int(sys.a
     v = torch.randn(pol.flat_params.numel(), device="cuda", dtype=torch.float64)
     ops.loss_grad(inp, keep_activations=True)
     out = dict(net=[do, da, 32], B=B)
+    abl = {"0": "", "1": "_no_acts_fetch", "2": "_no_x_fetch", "3": "_no_fetch"}[sys.argv[2] if len(sys.argv) > 2 else "0"]
     for rnd in range(3):
-        for tag, val, wps, abl in (("split32", "1", "0", "0"), ("split16_wps4", "3", "4", "0"), ("split16_wps3", "3", "3", "0"),
-                                   ("split16_wps4_no_acts_fetch", "3", "4", "1"), ("split16_wps4_no_x_fetch", "3", "4", "2"),
-                                   ("split16_wps4_no_fetch", "3", "4", "3"), ("split16_wps3_no_fetch", "3", "3", "3")):
+        for tag, val, wps in (("split32", "1", "0"), ("split16_wps4" + abl, "3", "4"), ("split16_wps3" + abl, "3", "3")):
             os.environ["RLLAB_FVP_SPLIT"] = val
             os.environ["RLLAB_FVP_SPLIT_WPS"] = wps
-            os.environ["RLLAB_SPLIT16_ABLATE"] = abl
             out.setdefault(tag + "_ms", []).append(round(timed(lambda: ops.fvp(inp, v)), 4))
     print(json.dumps(out), flush=True)
