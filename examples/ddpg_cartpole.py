@@ -7,6 +7,7 @@ kernel launch.
 
   python examples/ddpg_cartpole.py
   python examples/ddpg_cartpole.py --n-envs 8 --n-epochs 50 --csv ddpg.csv
+  python examples/ddpg_cartpole.py --n-envs 64 --rollout-steps 10      (collection and evaluation in the fused rollout)
 """
 import argparse
 import os
@@ -26,6 +27,9 @@ from rllab.q_functions.continuous_mlp_q_function import ContinuousMLPQFunction  
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-envs", type=int, default=1)
+    ap.add_argument("--rollout-steps", type=int, default=None,
+                    help="collect in launches of the fused rollout of this many lock-steps (default: one transition "
+                         "at a time)")
     ap.add_argument("--n-epochs", type=int, default=1000)
     ap.add_argument("--epoch-length", type=int, default=1000)
     ap.add_argument("--min-pool-size", type=int, default=10000)
@@ -61,6 +65,7 @@ def main():
         qf_learning_rate=1e-3,
         policy_learning_rate=1e-4,
         n_envs=args.n_envs,
+        rollout_steps=args.rollout_steps,
     )
     algo.train()
 

@@ -1063,6 +1063,69 @@ typedef struct rl_ddpg_args {
 size_t rl_ddpg_state_bytes(int obs_dim, int act_dim, int hidden0, int hidden1);   /* 0: a shape the kernel does not run */
 int rl_ddpg_update(const rl_ddpg_args* args, void* stream);
 
+/* Deterministic rollout: the fused rollout of a DeterministicMLPPolicy under an exploration strategy -- the collection
+ * and the evaluation rollouts of DDPG (rllab/algos/ddpg.py:214-246, rllab/exploration_strategies).  Env-per-lane like the
+ * recurrent rollout (rollout_det_kernel<Env>, csrc/det_mlp_kernels.hip): every env is stepped `horizon` times with
+ * auto-reset exactly as rl_rollout_gaussian_mlp steps it (same Philox streams keyed by (seed, env_offset + i,
+ * step_counter + t); the launch consumes horizon + 1 counters), its action coming from
+ *   m = out(act(act(o W0 + b0) W1 + b1) W2 + b2)     per unit: acc = b[j], acc = fmaf(x[k], W[k][j], acc) in input order
+ * and the exploration rule `explore`, on z = eps or the N(0, 1) draws of the policy stream, every operation rounded once
+ * in float32:
+ *   RL_EXPLORE_NONE      a = m (not clipped; no draws are made)
+ *   RL_EXPLORE_OU        x <- x + (ou_theta * (ou_mu - x) + ou_sigma * z),  a = max(min(m + x, high), low); x is one value
+ *                        per env and action, put back to ou_mu after any step that ended the path, carried between
+ *                        launches in explore_state: read when reset_at_start == 0, written by every launch
+ *   RL_EXPLORE_GAUSSIAN  a = max(min(m + z * sigma_t[t], high), low)
+ * theta: W0[D][hidden0] b0 W1[hidden0][hidden1] b1 W2[hidden1][A] b2 with every W stored [in][out] row-major and
+ * hidden0 / hidden1 the layer widths padded with zero weights and biases to a multiple of 4 (exact: a padded unit is 0).
+ * hidden0 / hidden1 must be multiples of 4 in 4 .. 64, hidden_activation RL_ACT_TANH / RL_ACT_RECTIFY, output_activation
+ * RL_ACT_TANH / RL_ACT_IDENTITY, low / high set when exploring, explore_state under RL_EXPLORE_OU and sigma_t under
+ * RL_EXPLORE_GAUSSIAN: anything else is RL_ERR_ARG.  An env of more than 32 observations or 8 actions is
+ * RL_ERR_UNSUPPORTED, as are the soft-constraint steps RL_CFG_LIMIT_MUJOCO / RL_CFG_CONTACT_MUJOCO of the legged envs and a
+ * request of more than 160 KB of LDS (rl_last_error has the byte count).  Nothing is launched on an error. */
+enum rl_explore { RL_EXPLORE_NONE = 0, RL_EXPLORE_OU = 1, RL_EXPLORE_GAUSSIAN = 2 };
+
+typedef struct rl_det_rollout_args {
+    int32_t kind;             /* rl_env_kind */
+    int32_t n_envs;
+    int32_t horizon;          /* T: steps per env in this call */
+    int32_t max_path_length;  /* forced done when ts reaches it */
+    int32_t normalize;        /* NormalizedEnv action map on/off */
+    int32_t reset_at_start;   /* 1: reset every env (and x) first; 0: carry on from the buffers below */
+    int32_t hidden0, hidden1; /* padded widths */
+    int32_t hidden_activation, output_activation;   /* enum rl_activation */
+    int32_t explore;          /* enum rl_explore */
+    int32_t env_offset;       /* global index of env 0 (RNG key) */
+    float scale_reward;
+    float ou_theta, ou_mu, ou_sigma;   /* RL_EXPLORE_OU */
+    uint64_t seed;
+    uint64_t step_counter;    /* global step index of t = 0 (RNG counter base) */
+    float* state;             /* float[state_dim][n]  in/out */
+    int32_t* ts;              /* int32[n]             in/out */
+    float* last_obs;          /* float[obs_dim][n]    in/out: the observation the next launch starts from */
+    float* explore_state;     /* float[act_dim][n]    in/out, RL_EXPLORE_OU (not touched otherwise) */
+    const float* theta;       /* device, the layout above */
+    const float* sigma_t;     /* device float[T], RL_EXPLORE_GAUSSIAN */
+    const float* low;         /* host float[act_dim]: the action space the strategy clips to (not the inner env's */
+    const float* high;        /* bounds under `normalize`); read when exploring */
+    const float* eps;         /* NULL or float[act_dim][T][n] injected N(0,1) exploration noise */
+    const float* reset_draws; /* NULL or float[T+1][reset_draws][n]: slice 0 = initial reset, slice t+1 = reset after step t */
+    const float* act_noise_z; /* NULL or float[T][act_dim][n] injected draws of the env's action noise */
+    const float* obs_noise_z; /* NULL or float[T+1][obs_dim][n] injected draws of the env's observation noise */
+    float* obs;               /* float[obs_dim][T][n] */
+    float* actions;           /* float[act_dim][T][n] */
+    float* means;             /* float[act_dim][T][n]: the network's output m */
+    float* rewards;           /* float[T][n] */
+    uint8_t* dones;           /* uint8[T][n] */
+    uint8_t* cuts;            /* NULL or uint8[T][n]: 1 where the path was cut at max_path_length and the env itself had not
+                               * terminated on that step (a transition on which the env terminates exactly at its
+                               * max_path_length-th step is a terminal, not a cut) */
+    const rl_env_cfg* cfg;    /* host; NULL = the env's defaults (its action_noise_z / obs_noise_z are not read here) */
+    const rl_launch_opts* opts;   /* host; NULL.  Reserved: the launch has one shape, 64 envs per single-wavefront workgroup */
+} rl_det_rollout_args;
+
+int rl_rollout_deterministic_mlp(const rl_det_rollout_args* args, void* stream);
+
 /* Debug / test hook: fill out[4*count] with Philox4x32-10 blocks for counters
  * (c0 + i, c1, c2, c3), key (k0, k1), i = 0..count-1.  Device buffer. */
 int rl_debug_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,

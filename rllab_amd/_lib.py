@@ -40,6 +40,7 @@ SYMBOLS = [
     "rl_mlp_forward", "rl_mlp_forward_ws", "rl_mlp_backward", "rl_gaussian_head_workspace_bytes", "rl_gaussian_head", "rl_gaussian_fisher",
     "rl_rollout_gridworld", "rl_rollout_gridworld_gru", "rl_categorical_softmax", "rl_categorical_head_workspace_bytes", "rl_categorical_head",
     "rl_categorical_fisher", "rl_cmaes_cov_update", "rl_ddpg_state_bytes", "rl_ddpg_update",
+    "rl_rollout_deterministic_mlp",
 ]
 
 
@@ -185,6 +186,29 @@ class DdpgArgs(ctypes.Structure):
 
 DDPG_ADAM, DDPG_SGD = 0, 1
 DDPG_STATS = 16            # doubles in rl_ddpg_args.stats
+
+
+class DetRolloutArgs(ctypes.Structure):
+    """Mirror of ``rl_det_rollout_args`` (include/rllab_amd.h): the fused rollout of a DeterministicMLPPolicy under an
+    exploration strategy."""
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("n_envs", ctypes.c_int32), ("horizon", ctypes.c_int32),
+        ("max_path_length", ctypes.c_int32), ("normalize", ctypes.c_int32), ("reset_at_start", ctypes.c_int32),
+        ("hidden0", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden_activation", ctypes.c_int32),
+        ("output_activation", ctypes.c_int32), ("explore", ctypes.c_int32), ("env_offset", ctypes.c_int32),
+        ("scale_reward", ctypes.c_float), ("ou_theta", ctypes.c_float), ("ou_mu", ctypes.c_float),
+        ("ou_sigma", ctypes.c_float), ("seed", ctypes.c_uint64), ("step_counter", ctypes.c_uint64),
+        ("state", ctypes.c_void_p), ("ts", ctypes.c_void_p), ("last_obs", ctypes.c_void_p),
+        ("explore_state", ctypes.c_void_p), ("theta", ctypes.c_void_p), ("sigma_t", ctypes.c_void_p),
+        ("low", ctypes.POINTER(ctypes.c_float)), ("high", ctypes.POINTER(ctypes.c_float)),
+        ("eps", ctypes.c_void_p), ("reset_draws", ctypes.c_void_p), ("act_noise_z", ctypes.c_void_p),
+        ("obs_noise_z", ctypes.c_void_p), ("obs", ctypes.c_void_p), ("actions", ctypes.c_void_p),
+        ("means", ctypes.c_void_p), ("rewards", ctypes.c_void_p), ("dones", ctypes.c_void_p),
+        ("cuts", ctypes.c_void_p), ("cfg", ctypes.POINTER(EnvCfg)), ("opts", ctypes.c_void_p),
+    ]
+
+
+EXPLORE_NONE, EXPLORE_OU, EXPLORE_GAUSSIAN = 0, 1, 2
 
 
 class PolicyBatch(ctypes.Structure):
@@ -377,6 +401,7 @@ def _load():
     lib.rl_ddpg_state_bytes.restype = sz
     lib.rl_ddpg_state_bytes.argtypes = [i32, i32, i32, i32]
     lib.rl_ddpg_update.argtypes = [vp, vp]
+    lib.rl_rollout_deterministic_mlp.argtypes = [vp, vp]
     vpp = ctypes.POINTER(ctypes.c_void_p)
     lib.rl_peer_mailbox_bytes.restype = sz
     lib.rl_peer_mailbox_bytes.argtypes = [i32, i32]

@@ -14,9 +14,14 @@ Paths: a path ends when the env terminates or, counted here per env, at ``max_pa
 transition the reference adds to its pool only under ``include_horizon_terminal_transitions``; every env writes one
 pool row per step, so such a row is written with ``skip = 1`` and the batch draw passes over it.
 
-Evaluation samples ``eval_samples`` steps with the project's ``VectorizedSampler`` (the per-transition loop: there is no
-rollout kernel for a deterministic policy) and reads the update statistics -- sums accumulated on the device by the
-kernel -- once per epoch.
+Evaluation samples ``eval_samples`` steps with the project's ``VectorizedSampler`` (the per-transition loop by default)
+and reads the update statistics -- sums accumulated on the device by the kernel -- once per epoch.
+
+``rollout_steps=S`` moves the sampling into rl_rollout_deterministic_mlp (``HipVecEnv.rollout_deterministic``): the
+collection runs in launches of up to S lock-steps -- policy, exploration noise, env step, auto-reset and the cut at
+``max_path_length`` inside the kernel -- each followed by ONE write of its ``S * n_envs`` rows into the pool and ONE
+launch of the updates those lock-steps earn (``chunk_update_count``); the evaluation rollouts take the same kernel
+without exploration.
 """
 import math
 import pickle
@@ -26,9 +31,19 @@ import torch
 
 import rllab_amd.misc.logger as logger
 from rllab_amd.algos.base import RLAlgorithm
-from rllab_amd.algos.ddpg_update import FusedDDPGUpdate, ddpg_why_unsupported, parse_update_method
+from rllab_amd.algos.ddpg_update import MAX_UPDATES, FusedDDPGUpdate, ddpg_why_unsupported, parse_update_method
 from rllab_amd.algos.replay_pool import DeviceReplayPool
 from rllab_amd.misc import ext, special
+
+
+def chunk_update_count(size, n_envs, steps, min_pool_size, capacity):
+    """How many of the ``steps`` lock-steps of a chunk are followed by updates in the lock-step loop: those after which
+    the pool, ``size`` rows before the chunk and ``n_envs`` more per lock-step up to ``capacity``, holds at least
+    ``min_pool_size`` rows."""
+    if capacity < min_pool_size:
+        return 0
+    first = max(1, -(-(int(min_pool_size) - int(size)) // int(n_envs)))       # the first lock-step that reaches it
+    return max(0, int(steps) - first + 1)
 
 
 class _EvalView(object):
@@ -37,6 +52,23 @@ class _EvalView(object):
 
     def __init__(self, env, policy, batch_size, max_path_length):
         self.env, self.policy, self.batch_size, self.max_path_length = env, policy, batch_size, max_path_length
+
+
+class _FusedEvalSampler(object):
+    """Mixed into ``VectorizedSampler`` for ``DDPG(rollout_steps=...)``: the evaluation rollouts are launches of
+    rl_rollout_deterministic_mlp without exploration.  The whole-paths contract is the sampler's own: further launches
+    carry the same envs on (``reset_at_start=False``) until ``eval_samples`` samples are in finished paths."""
+
+    def _takes_fused_rollout(self, policy):
+        return self.vec_env is not None
+
+    def sampling_path(self, policy):
+        if self.vec_env is None:
+            return "none (no executor yet)", None
+        return "fused deterministic rollout kernel (one launch per batch of %d envs)" % self.vec_env.n, None
+
+    def _rollout_chunk(self, policy, steps, first):
+        return self.vec_env.rollout_deterministic(policy, steps, reset_at_start=first)
 
 
 class DDPG(RLAlgorithm):
@@ -69,7 +101,8 @@ class DDPG(RLAlgorithm):
             plot=False,
             pause_for_plot=False,
             *,
-            n_envs=1):
+            n_envs=1,
+            rollout_steps=None):
         """Arguments as the reference's constructor takes them (rllab/algos/ddpg.py:89-115): ``batch_size`` rows per
         update, ``n_epochs`` epochs of ``epoch_length`` collected steps with an evaluation of ``eval_samples`` steps after
         each, updates once the pool holds ``min_pool_size`` of its ``replay_pool_size`` rows, paths cut at
@@ -78,7 +111,13 @@ class DDPG(RLAlgorithm):
         multiplied by ``scale_reward`` when stored, ``include_horizon_terminal_transitions`` keeps the transitions
         that end a path at ``max_path_length``.  ``soft_target`` and ``pause_for_plot`` are accepted and unused, as in
         the reference; ``plot=True`` is refused.  Keyword-only ``n_envs``: env copies that collect in lock step, each
-        step followed by ``n_envs * n_updates_per_sample`` updates in one launch."""
+        step followed by ``n_envs * n_updates_per_sample`` updates in one launch.  Keyword-only ``rollout_steps``:
+        None (the default) collects and evaluates one transition at a time, as described above.  ``S >= 1`` collects in
+        launches of the fused rollout of ``min(S, lock-steps left in the epoch)`` lock-steps, each followed by one pool
+        write and one launch of all the updates its lock-steps earn -- the same ratio of updates to samples -- and
+        evaluates with the same kernel.  The exploring actions of a launch all come from the policy as of its start:
+        ``S = 1`` is the lock-step loop's order exactly, ``S > 1`` trades policy freshness (the policy acts up to
+        ``S - 1`` lock-steps behind its updates, which in turn see the whole chunk in the pool) for fewer launches."""
         self.env = env
         self.policy = policy
         self.qf = qf
@@ -103,6 +142,7 @@ class DDPG(RLAlgorithm):
         self.plot = plot
         self.pause_for_plot = pause_for_plot
         self.n_envs = int(n_envs)
+        self.rollout_steps = None if rollout_steps is None else int(rollout_steps)
         self.scale_reward = scale_reward
         self.opt_info = None
         self.itr = 0
@@ -127,16 +167,43 @@ class DDPG(RLAlgorithm):
                     "part of the DDPG collection loop")
         if self.n_envs > int(self.replay_pool_size):
             return "n_envs=%d exceeds replay_pool_size=%d" % (self.n_envs, self.replay_pool_size)
-        return ddpg_why_unsupported(self.policy, self.qf, self.batch_size, self.n_envs * int(self.n_updates_per_sample))
+        why = ddpg_why_unsupported(self.policy, self.qf, self.batch_size, self.n_envs * int(self.n_updates_per_sample))
+        if why is not None or self.rollout_steps is None:
+            return why
+        if self.rollout_steps < 1:
+            return "rollout_steps=%d: a launch of the fused collection rollout runs at least one lock-step" % \
+                self.rollout_steps
+        if not hasattr(self.es, "kernel_rule"):
+            return "rollout_steps: %s has no rule inside the deterministic rollout kernel (OUStrategy and " \
+                   "GaussianStrategy have)" % type(self.es).__name__
+        steps = min(self.rollout_steps, int(math.ceil(self.epoch_length / float(self.n_envs))))
+        if steps * self.n_envs > int(self.replay_pool_size):
+            return "rollout_steps: a launch of %d lock-steps of %d envs writes %d rows, replay_pool_size is %d" % (
+                steps, self.n_envs, steps * self.n_envs, self.replay_pool_size)
+        most = steps * self.n_envs * int(self.n_updates_per_sample)
+        if most > MAX_UPDATES:
+            return "rollout_steps: %d updates after a launch of %d lock-steps (n_envs * n_updates_per_sample each): one " \
+                   "launch of the DDPG update kernel runs 1 .. %d" % (most, steps, MAX_UPDATES)
+        return None
 
     # -- set-up -------------------------------------------------------------------------------------------------------
     def start_worker(self):
         """The collection executor (``n_envs`` copies, paths cut here, not by the executor) and the evaluation sampler."""
         from rllab_amd.sampler.vectorized_sampler import VectorizedSampler
-        self.vec_env = self.env.vec_env_executor(n_envs=self.n_envs, max_path_length=0)
+        fused = self.rollout_steps is not None
+        # (the fused collection rollout cuts the paths inside the kernel)
+        self.vec_env = self.env.vec_env_executor(n_envs=self.n_envs, max_path_length=self.max_path_length if fused else 0)
         view = _EvalView(self.env, self.policy, self.eval_samples, self.max_path_length)
-        self.eval_sampler = VectorizedSampler(view, use_graph=False)     # no captured graph in this algorithm
+        sampler_cls = type("FusedEvalSampler", (_FusedEvalSampler, VectorizedSampler), {}) if fused else VectorizedSampler
+        self.eval_sampler = sampler_cls(view, use_graph=False)     # no captured graph in this algorithm
         self.eval_sampler.start_worker()
+        if fused:
+            for vec in (self.vec_env, self.eval_sampler.vec_env):
+                why = vec.why_no_deterministic_rollout()
+                if why is not None:
+                    raise NotImplementedError("DDPG(rollout_steps=%d): %s" % (self.rollout_steps, why))
+            logger.log("collection: fused deterministic rollout, launches of up to %d lock-steps of %d envs" % (
+                self.rollout_steps, self.n_envs))
 
     def init_opt(self):
         # the "target" policy and Q function of the reference are planes of the kernel's state; these two objects
@@ -163,7 +230,9 @@ class DDPG(RLAlgorithm):
         steps_per_epoch = int(math.ceil(self.epoch_length / float(n)))
         # exploration returns of the paths that end in an epoch: NaN where no path ended
         self._es_returns = torch.full((steps_per_epoch, n), float("nan"), dtype=torch.float64, device=dev)
-        observation = vec.reset().clone()
+        fused = self.rollout_steps is not None
+        if not fused:
+            observation = vec.reset().clone()
         self.es.reset()
         horizon_rows_skip = 0.0 if self.include_horizon_terminal_transitions else 1.0
 
@@ -171,27 +240,30 @@ class DDPG(RLAlgorithm):
             logger.push_prefix('epoch #%d | ' % epoch)
             logger.log("Training started")
             self._es_returns.fill_(float("nan"))
-            for epoch_itr in range(steps_per_epoch):
-                # the policy the actions come from is self.policy: its parameters move only where the reference
-                # refreshes its sample_policy, right after the updates of a step
-                action = self.es.get_actions(self.itr, observation, policy=self.policy)
-                next_observation, reward, done, _ = vec.step(action)   # envs that terminated come back reset
-                path_length += 1
-                path_return += reward.to(torch.float64)
-                horizon = (~done) & (path_length >= self.max_path_length)
-                terminal = done | horizon
-                pool.add(observation, action, reward * self.scale_reward, terminal, next_observation,
-                         horizon.to(torch.float32) * horizon_rows_skip)
-                # the envs whose path was cut here start over (a launch over a mask of zeros when nobody was cut)
-                observation = vec.reset(mask=horizon).clone()
-                self.es.reset(mask=terminal)
-                self._es_returns[epoch_itr] = torch.where(terminal, path_return, self._es_returns[epoch_itr])
-                path_length.masked_fill_(terminal, 0)
-                path_return.masked_fill_(terminal, 0.0)
+            if fused:
+                self._collect_fused(steps_per_epoch, path_return, first=(epoch == 0))
+            else:
+                for epoch_itr in range(steps_per_epoch):
+                    # the policy the actions come from is self.policy: its parameters move only where the reference
+                    # refreshes its sample_policy, right after the updates of a step
+                    action = self.es.get_actions(self.itr, observation, policy=self.policy)
+                    next_observation, reward, done, _ = vec.step(action)   # envs that terminated come back reset
+                    path_length += 1
+                    path_return += reward.to(torch.float64)
+                    horizon = (~done) & (path_length >= self.max_path_length)
+                    terminal = done | horizon
+                    pool.add(observation, action, reward * self.scale_reward, terminal, next_observation,
+                             horizon.to(torch.float32) * horizon_rows_skip)
+                    # the envs whose path was cut here start over (a launch over a mask of zeros when nobody was cut)
+                    observation = vec.reset(mask=horizon).clone()
+                    self.es.reset(mask=terminal)
+                    self._es_returns[epoch_itr] = torch.where(terminal, path_return, self._es_returns[epoch_itr])
+                    path_length.masked_fill_(terminal, 0)
+                    path_return.masked_fill_(terminal, 0.0)
 
-                if pool.size >= self.min_pool_size:
-                    self.do_training(self.itr, pool)
-                self.itr += n
+                    if pool.size >= self.min_pool_size:
+                        self.do_training(self.itr, pool)
+                    self.itr += n
 
             logger.log("Training finished")
             if pool.size >= self.min_pool_size:
@@ -205,11 +277,52 @@ class DDPG(RLAlgorithm):
         if self.eval_sampler is not None:
             self.eval_sampler.shutdown_worker()
 
-    def do_training(self, itr, pool):
-        """The ``n_envs * n_updates_per_sample`` updates of one lock-step: one launch; then the acting policy's
-        parameters are refreshed from the kernel's state."""
+    def _collect_fused(self, steps_per_epoch, path_return, first):
+        """One epoch of collection in launches of rl_rollout_deterministic_mlp.  Per launch of T lock-steps: the T * n
+        rows go into the pool in one write, t-major -- ``next_obs`` is the observation plane one lock-step later (the
+        carried last observation for the last row; behind a row with ``term = 1`` that is the next path's first
+        observation, which the targets never read) -- then the updates its lock-steps earn run in one launch.
+        ``path_return`` [n] float64: the running paths' returns so far, carried from launch to launch."""
+        vec, pool, n = self.vec_env, self.pool, self.n_envs
+        skip_scale = 0.0 if self.include_horizon_terminal_transitions else 1.0
+        lock_step = 0
+        while lock_step < steps_per_epoch:
+            T = min(self.rollout_steps, steps_per_epoch - lock_step)
+            traj = vec.rollout_deterministic(self.policy, T, es=self.es, itr=self.itr,
+                                             reset_at_start=first and lock_step == 0)
+            k = n * int(self.n_updates_per_sample) * chunk_update_count(pool.size, n, T, self.min_pool_size,
+                                                                        pool.capacity)
+            rows = lambda planes: planes.permute(1, 2, 0).reshape(T * n, -1)
+            next_obs = torch.cat([traj.obs[:, 1:, :], vec._obs.unsqueeze(1)], dim=1)
+            pool.add(rows(traj.obs), rows(traj.actions), traj.rewards.reshape(-1) * self.scale_reward,
+                     traj.dones.reshape(-1), rows(next_obs), traj.cuts.reshape(-1).to(torch.float32) * skip_scale)
+            self._es_returns[lock_step:lock_step + T] = self._path_returns(traj.rewards, traj.dones, path_return)
+            if k > 0:
+                self.do_training(self.itr, pool, k)
+            self.itr += n * T
+            lock_step += T
+
+    @staticmethod
+    def _path_returns(rewards, dones, carry):
+        """[T, n] float64: the return of the path that ends at (t, env), NaN elsewhere, from a launch's reward and done
+        planes; ``carry`` [n] float64 -- what the paths running at the launch's start had collected -- is updated in
+        place to what the paths running at its end have."""
+        T = rewards.shape[0]
+        done = dones.bool()
+        csum = torch.cumsum(rewards.to(torch.float64), dim=0)
+        steps = torch.arange(T, device=rewards.device).unsqueeze(1)
+        last = torch.cummax(torch.where(done, steps, torch.full_like(steps, -1)), dim=0).values    # newest end up to t
+        before = torch.cat([torch.full_like(last[:1], -1), last[:-1]], dim=0)                      # ... ahead of t
+        since = lambda prev, upto: upto - torch.where(prev >= 0, csum.gather(0, prev.clamp(min=0)), -carry.unsqueeze(0))
+        out = torch.where(done, since(before, csum), torch.full_like(csum, float("nan")))
+        carry.copy_(since(last[-1:], csum[-1:])[0])
+        return out
+
+    def do_training(self, itr, pool, k=None):
+        """The ``n_envs * n_updates_per_sample`` updates of one lock-step (``k``: of the lock-steps of a fused launch):
+        one launch; then the acting policy's parameters are refreshed from the kernel's state."""
         update = self.opt_info["update"]
-        k = self.n_envs * int(self.n_updates_per_sample)
+        k = self.n_envs * int(self.n_updates_per_sample) if k is None else int(k)
         update.update(pool, k, discount=self.discount, tau=self.soft_target_tau,
                       qf_learning_rate=self.qf_learning_rate, policy_learning_rate=self.policy_learning_rate,
                       qf_weight_decay=self.qf_weight_decay, policy_weight_decay=self.policy_weight_decay,

@@ -12,6 +12,9 @@ per plane at the rows ``(top + i) mod capacity``.
 * ``skip`` is 1 on the rows the reference would not have added (a path cut at ``max_path_length`` while
   ``include_horizon_terminal_transitions`` is false): the row is written, because every env writes one row per step,
   and the batch draw of rl_ddpg_update passes over it.
+* ``next_obs`` of a row with ``term = 1`` is not specified: the lock-step loop stores the env's own successor there, a
+  launch of the fused collection rollout (``DDPG(rollout_steps=...)``) the first observation of the next path.  The
+  targets y = rew + (1 - term) * discount * Q'(next_obs, ..) never read it.
 
 Difference from the reference, on purpose: SimpleReplayPool stores no successor observation and reads row ``index + 1``
 instead, which after a dropped horizon transition pairs the last kept transition of a path with the first observation

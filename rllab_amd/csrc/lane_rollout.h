@@ -17,6 +17,12 @@
 // Optional: static constexpr bool DELAYS_ACTIONS = true and
 //   delayed(act, applied)               the action the env is stepped with in place of the policy's own `act` (recorded,
 //                                       and handed to stepped(), as ever); once per step, ahead of Env::step
+// Optional: static constexpr bool EXPLORES = true and
+//   needs_draws()                       false: the step's N(0, 1) draws z are not made (wave-uniform; z is zeros then)
+//   explore(mean, z, act)               forms the action from the mean and the draws, in place of act = z * std(k) + mean
+//                                       (std() is not asked for then)
+// Optional: static constexpr bool HEARS_ENV_DONE = true and
+//   env_done(d)                         the env's own done of this step, ahead of the cut forced at max_path_length
 // A policy without the member is compiled exactly as before.
 #pragma once
 #include <type_traits>
@@ -28,6 +34,14 @@ template <class Policy, class = void>
 struct delays_actions : std::false_type {};
 template <class Policy>
 struct delays_actions<Policy, std::void_t<decltype(Policy::DELAYS_ACTIONS)>> : std::bool_constant<Policy::DELAYS_ACTIONS> {};
+template <class Policy, class = void>
+struct explores : std::false_type {};
+template <class Policy>
+struct explores<Policy, std::void_t<decltype(Policy::EXPLORES)>> : std::bool_constant<Policy::EXPLORES> {};
+template <class Policy, class = void>
+struct hears_env_done : std::false_type {};
+template <class Policy>
+struct hears_env_done<Policy, std::void_t<decltype(Policy::HEARS_ENV_DONE)>> : std::bool_constant<Policy::HEARS_ENV_DONE> {};
 
 // the by-value kernel arguments every such launch has
 struct LaneRolloutDev {
@@ -101,15 +115,24 @@ __device__ __forceinline__ void rollout_lane(const LaneRolloutDev& a, int i, Pol
         if (ALL || a.obs) store_planes<DO>(a.obs + row, plane, lane_f32, o);
         float mean[DA], act[DA], z[DA];
         pol.mean(o, mean);
-        if (a.eps) {
+        bool draws = true;
+        if constexpr (explores<Policy>::value) draws = pol.needs_draws();
+        if (!draws) {
+#pragma unroll
+            for (int k = 0; k < DA; ++k) z[k] = 0.0f;
+        } else if (a.eps) {
 #pragma unroll
             for (int k = 0; k < DA; ++k) z[k] = a.eps[k * plane + off_t];
             landed<DA>(z);
         } else {
             philox_draws<DA, true>(z, a.seed, env_global, a.step_counter + (uint64_t)t, RNG_POLICY);
         }
+        if constexpr (explores<Policy>::value) {
+            pol.explore(mean, z, act);
+        } else {
 #pragma unroll
-        for (int k = 0; k < DA; ++k) act[k] = __builtin_fmaf(z[k], pol.std(k), mean[k]);  // rnd * exp(log_std) + mean
+            for (int k = 0; k < DA; ++k) act[k] = __builtin_fmaf(z[k], pol.std(k), mean[k]);  // rnd * exp(log_std) + mean
+        }
         if (ALL || a.actions) store_planes<DA>(a.actions + row, plane, lane_f32, act);
         if (ALL || a.means) store_planes<DA>(a.means + row, plane, lane_f32, mean);
 
@@ -127,6 +150,7 @@ __device__ __forceinline__ void rollout_lane(const LaneRolloutDev& a, int i, Pol
                           a.step_counter + (uint64_t)t, o, r, d);
         }
         ts += 1;
+        if constexpr (hears_env_done<Policy>::value) pol.env_done(d);
         if (a.max_path_length > 0 && ts >= a.max_path_length) d = true;
         const float rs = r * a.scale_reward;
         const uint8_t db = d ? 1 : 0;

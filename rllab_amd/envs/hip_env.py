@@ -445,6 +445,82 @@ class HipVecEnv(object):
         return Trajectories(obs, act, mean, policy.recorded_log_std(), rew, done, self.max_path_length,
                             prev_action_info=bool(policy.state_include_action))
 
+    # -- deterministic rollout: a DeterministicMLPPolicy under an exploration strategy --------
+    def why_no_deterministic_rollout(self):
+        """One sentence naming what keeps this executor off rl_rollout_deterministic_mlp, or None."""
+        if self.position_ids is not None:
+            return "kept observation rows (Box2DEnv(position_only=True) / OcclusionEnv) are not built into the " \
+                   "deterministic rollout kernel"
+        if self.action_delay:
+            return "DelayedActionEnv: the action queue is built into the recurrent rollout kernel only"
+        return None
+
+    def rollout_deterministic(self, policy, horizon, es=None, itr=0, reset_at_start=True, eps=None, reset_draws=None,
+                              action_noise_z=None, obs_noise_z=None):
+        """``horizon`` lock-step iterations of policy -> exploration -> step -> record -> auto-reset in ONE launch
+        (rl_rollout_deterministic_mlp).  ``policy``: a DeterministicMLPPolicy; ``es``: an OUStrategy or a
+        GaussianStrategy applied inside the kernel (``es.kernel_rule``; lock-step t is the strategy's time
+        ``itr + t * n``), or None: the actions are the policy's own (evaluation).  An OUStrategy's ``states`` [n, Da]
+        are what the launch starts from (unless ``reset_at_start``) and are left where it ends, for the next launch or
+        the next ``get_actions``.  Returns ``Trajectories`` (``means``: the network's output, ``log_std``:
+        ``policy.recorded_log_std()``) with an extra ``cuts`` attribute, uint8 [T, n]: 1 where the path was cut at
+        ``max_path_length`` and the env itself had not terminated.  The injected-noise keywords are those of
+        ``rollout``; ``eps`` are the strategy's N(0, 1) draws."""
+        why = self.why_no_deterministic_rollout()
+        if why is not None:
+            raise NotImplementedError("rollout_deterministic: %s" % why)
+        T, n = int(horizon), self.n
+        do, da = self.q["obs_dim"], self.q["act_dim"]
+        if (policy.obs_dim, policy.action_dim) != (do, da):
+            raise ValueError("policy built for another env: this executor's has %d observations and %d actions, the "
+                             "policy's %d and %d" % (do, da, policy.obs_dim, policy.action_dim))
+        theta, (h0, h1), (act_hidden, act_out) = policy.rollout_layout()
+        assert theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous()
+        f32 = dict(dtype=torch.float32, device=self.device)
+        rule = dict(code=_lib.EXPLORE_NONE, theta=0.0, mu=0.0, sigma=0.0, low=None, high=None, sigma_t=None) \
+            if es is None else es.kernel_rule(int(itr), T, n, self.device)
+        x = None
+        if rule["code"] == _lib.EXPLORE_OU:
+            # explore_state [Da, n]: the strategy's states transposed (its own memory once a launch has left them)
+            if es.states is None or tuple(es.states.shape) != (n, da) or es.states.device != self.device:
+                if not reset_at_start:
+                    raise ValueError("rollout_deterministic(reset_at_start=False) under an OUStrategy needs the states "
+                                     "[n, Da] a previous launch or get_actions left on the strategy")
+                es.states = torch.full((n, da), rule["mu"], **f32)
+            x = es.states.to(torch.float32).t().contiguous()
+        bound = lambda b: None if b is None else (ctypes.c_float * da)(*[float(v) for v in b])
+        low, high = bound(rule["low"]), bound(rule["high"])
+        obs = torch.empty((do, T, n), **f32)
+        act = torch.empty((da, T, n), **f32)
+        mean = torch.empty((da, T, n), **f32)
+        rew = torch.empty((T, n), **f32)
+        done = torch.empty((T, n), dtype=torch.uint8, device=self.device)
+        cuts = torch.empty((T, n), dtype=torch.uint8, device=self.device)
+        eps = self._plane(eps, (da, T, n))
+        reset_draws = self._plane(reset_draws, (T + 1, self.q["reset_draws"], n))
+        az = self._plane(action_noise_z, (T, da, n))
+        oz = self._plane(obs_noise_z, (T + 1, do, n))
+        p = lambda t: None if t is None else t.data_ptr()
+        self._cfg_with(None, None)
+        args = _lib.DetRolloutArgs(
+            kind=self.kind, n_envs=n, horizon=T, max_path_length=self.max_path_length, normalize=int(self.normalize),
+            reset_at_start=int(bool(reset_at_start)), hidden0=h0, hidden1=h1, hidden_activation=act_hidden,
+            output_activation=act_out, explore=rule["code"], env_offset=self.env_offset, scale_reward=self.scale_reward,
+            ou_theta=rule["theta"], ou_mu=rule["mu"], ou_sigma=rule["sigma"], seed=self.seed,
+            step_counter=self.step_counter, state=self.state.data_ptr(), ts=self.ts.data_ptr(),
+            last_obs=self._obs.data_ptr(), explore_state=p(x), theta=theta.data_ptr(), sigma_t=p(rule["sigma_t"]),
+            low=low, high=high, eps=p(eps), reset_draws=p(reset_draws), act_noise_z=p(az), obs_noise_z=p(oz),
+            obs=obs.data_ptr(), actions=act.data_ptr(), means=mean.data_ptr(), rewards=rew.data_ptr(),
+            dones=done.data_ptr(), cuts=cuts.data_ptr(), cfg=ctypes.pointer(self.cfg), opts=_lib.launch_opts())
+        _lib.check(_lib.lib.rl_rollout_deterministic_mlp(ctypes.byref(args), _lib.stream_ptr()),
+                   "rl_rollout_deterministic_mlp")
+        self.step_counter += T + 1            # as rollout(): counter T belongs to the reset after the last step
+        if x is not None:
+            es.states = x.t()
+        traj = Trajectories(obs, act, mean, policy.recorded_log_std(), rew, done, self.max_path_length)
+        traj.cuts = cuts
+        return traj
+
     # -- population rollout: one parameter vector per env ---------------------------
     def rollout_population(self, theta_pop, n_evals, horizon, discount, record=True, eps=None, reset_draws=None,
                            action_noise_z=None, obs_noise_z=None, layer_activations=0, log_min_std=None):

@@ -203,6 +203,10 @@ class NormalizingVecEnv(object):
         return self.inner.rollout(policy, horizon, reset_at_start=reset_at_start, norm=self,
                                   scale_reward=self.scale_reward_outer, **kwargs)
 
+    def rollout_deterministic(self, policy, horizon, **kwargs):
+        raise NotImplementedError("rollout_deterministic: NormalizedEnv(normalize_obs / normalize_reward): the running "
+                                  "estimates are not built into the deterministic rollout kernel")
+
     def snapshot(self):
         """Everything a launch or a step advances -- the four estimate planes, the env state, the steps since the reset,
         the carried observation and the RNG counter -- as copies ``restore`` puts back: the sampler takes a launch back

@@ -27,6 +27,18 @@ class GaussianStrategy(ExplorationStrategy, Serializable):
         return np.clip(action + np.random.normal(size=len(action)) * self.sigma(t), self._action_space.low,
                        self._action_space.high)
 
+    def kernel_rule(self, itr, horizon, n_envs, device):
+        """What rl_rollout_deterministic_mlp needs to apply this strategy inside a launch of ``horizon`` lock-steps of
+        ``n_envs`` envs that starts at ``itr``: the rule's code, the bounds it clips to and the device plane
+        ``sigma_t`` [horizon] = sigma(itr + t * n_envs) rounded to float32 -- lock-step t of the launch is DDPG's
+        ``itr + t * n_envs``."""
+        from rllab_amd import _lib
+        sigma_t = np.asarray([self.sigma(itr + t * n_envs) for t in range(int(horizon))], dtype=np.float32)
+        return dict(code=_lib.EXPLORE_GAUSSIAN, theta=0.0, mu=0.0, sigma=0.0,
+                    low=np.asarray(self._action_space.low, dtype=np.float32),
+                    high=np.asarray(self._action_space.high, dtype=np.float32),
+                    sigma_t=torch.as_tensor(sigma_t).to(device))
+
     def get_actions(self, t, observations, policy, normals=None, **kwargs):
         actions, _ = policy.get_actions(observations)
         if normals is None:

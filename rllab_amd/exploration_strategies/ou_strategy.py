@@ -64,6 +64,15 @@ class OUStrategy(ExplorationStrategy, Serializable):
         self.states = x + (self.theta * (self.mu - x) + self.sigma * normals)
         return self.states
 
+    def kernel_rule(self, itr, horizon, n_envs, device):
+        """What rl_rollout_deterministic_mlp needs to apply this strategy inside a launch of ``horizon`` lock-steps of
+        ``n_envs`` envs: the rule's code, its scalars and the bounds it clips to.  The executor keeps ``states`` [n, Da]
+        as the state the launch starts from and ends on (``HipVecEnv.rollout_deterministic``)."""
+        from rllab_amd import _lib
+        return dict(code=_lib.EXPLORE_OU, theta=float(self.theta), mu=float(self.mu), sigma=float(self.sigma),
+                    low=np.asarray(self.action_space.low, dtype=np.float32),
+                    high=np.asarray(self.action_space.high, dtype=np.float32), sigma_t=None)
+
     def get_actions(self, t, observations, policy, normals=None, **kwargs):
         """observations [n, Do] tensor -> actions [n, Da] tensor on the same device; ``normals``: injected draws."""
         actions, _ = policy.get_actions(observations)

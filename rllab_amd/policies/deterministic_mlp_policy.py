@@ -98,6 +98,50 @@ class DeterministicMLPPolicy(Policy, Serializable):
         spread, log(0)."""
         return torch.full((self.action_dim,), float("-inf"), dtype=torch.float32, device=self.flat_params.device)
 
+    # -- the fused rollout (rl_rollout_deterministic_mlp) ----------------------------------------------------------------
+    def why_no_rollout_layout(self):
+        """One sentence naming what keeps this network off rl_rollout_deterministic_mlp, or None: the kernel runs the
+        shapes the DDPG update kernel runs."""
+        from rllab_amd import _lib
+        from rllab_amd.algos.ddpg_update import MAX_ACT, MAX_HIDDEN, MAX_OBS, _activation_code
+        hs = self.hidden_sizes
+        if len(hs) != 2 or not all(1 <= h <= MAX_HIDDEN for h in hs):
+            return "hidden_sizes=%r: the deterministic rollout kernel runs two hidden layers of 1 .. %d units" % (
+                tuple(hs), MAX_HIDDEN)
+        if self.obs_dim > MAX_OBS or self.action_dim > MAX_ACT:
+            return "obs_dim %d, act_dim %d: the deterministic rollout kernel runs at most %d observation and %d action " \
+                   "entries" % (self.obs_dim, self.action_dim, MAX_OBS, MAX_ACT)
+        hidden, why = _activation_code(self.hidden_nonlinearity, "the hidden_nonlinearity", "rectify or tanh")
+        if why is None and hidden == _lib.ACT_IDENTITY:
+            why = "the hidden_nonlinearity is the identity: the deterministic rollout kernel evaluates rectify or tanh"
+        if why is not None:
+            return why
+        out, why = _activation_code(self.output_nonlinearity, "the output_nonlinearity", "tanh or the identity")
+        if why is None and out == _lib.ACT_RECTIFY:
+            why = "the output_nonlinearity is rectify: the deterministic rollout kernel evaluates tanh or the identity"
+        return why
+
+    def rollout_layout(self):
+        """``(theta, (H0p, H1p), (hidden code, output code))`` for rl_rollout_deterministic_mlp: the parameters as one
+        flat float32 vector W0[D][H0p] b0 W1[H0p][H1p] b1 W2[H1p][A] b2 on the device of ``flat_params``, each hidden
+        width padded to a multiple of 4 with zero weights and biases (a padded unit is act(0) = 0 and feeds zero rows:
+        exact).  Built from ``flat_params`` as they are now by one scatter on the device: no host synchronisation."""
+        from rllab_amd.algos.ddpg_update import _activation_code, _net_index
+        why = self.why_no_rollout_layout()
+        if why is not None:
+            raise NotImplementedError("DeterministicMLPPolicy: %s" % why)
+        h0, h1 = self.hidden_sizes
+        H0, H1 = (h0 + 3) // 4 * 4, (h1 + 3) // 4 * 4
+        flat = self.flat_params
+        cached = self.__dict__.get("_rollout_index")
+        if cached is None or cached[0].device != flat.device:
+            idx, total = _net_index(self.obs_dim, h0, h1, H0, H1, 0, self.action_dim, 0)
+            cached = self._rollout_index = (torch.as_tensor(idx, device=flat.device), int(total))
+        theta = torch.zeros(cached[1], dtype=torch.float32, device=flat.device)
+        theta[cached[0]] = flat.detach().to(torch.float32)
+        codes = (_activation_code(self.hidden_nonlinearity, "", "")[0], _activation_code(self.output_nonlinearity, "", "")[0])
+        return theta, (H0, H1), codes
+
     def why_no_kernel_layout(self):
         """The sentence the sampler logs for a policy it steps one transition at a time."""
         return "DeterministicMLPPolicy has no rollout kernel (a fused DDPG collection rollout is not built)"
